@@ -13,6 +13,10 @@ N > 1 (one process per GPU, RCCL; --config 4a, the default): configs[3], STRONG 
   pipelined over t chunks behind the GEMMs.  value = global flops / max-over-ranks time; rank 0
   then runs the same global problem alone (strong_scaling_vs_1gpu).  --config 4b: v1 split over
   t only, redistributed by an all-to-all inside the contraction.
+A plain run sets up, warms up, times --steps steps and prints the result line (--dump-outputs DIR
+  also writes what the last timed step computed, rank 0's tNSns output, as DIR/<name>.npy; the
+  inputs are a hash of the global index, the same in every run).  Everything below is measured
+  with --full only.
 Side measurements (extra fields): N = 1 -- the dist.cpp permute xyztsc -> tnsxyzc (64 slices),
   the 16^4 3x3-block BSR SpMM at n = 1 / 12 / 64 (config 3), the configs[4] chain on one GPU's
   share, the opt-in 3M complex form; N > 1 -- the configs[4] chain over the ranks, the 4b
@@ -101,6 +105,31 @@ def rel_err(a, b):
     """Normwise relative difference ||a - b|| / ||b|| (complex, any dtype)."""
     a, b = a.to(torch.complex128), b.to(torch.complex128)
     return (torch.linalg.vector_norm(a - b) / torch.linalg.vector_norm(b)).item()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(outdir, tensors):
+    """Write each named tensor as outdir/<name>.npy in float64 (float32 for single-precision
+    ones), a complex tensor as (re, im) pairs in a trailing dimension of 2.  All files together
+    stay within DUMP_MAX_BYTES: a tensor over its share is written as a fixed sample, the elements
+    at sorted indices drawn once from DUMP_SEED (the same for the same shape in every run)."""
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(tensors), 1)
+    for name, t in tensors.items():
+        t = t.detach().reshape(-1)
+        single = t.dtype in (torch.float32, torch.complex64, torch.float16, torch.bfloat16)
+        per_el = (4 if single else 8) * (2 if t.is_complex() else 1)
+        if t.numel() * per_el > share:
+            idx = np.random.default_rng(DUMP_SEED).choice(t.numel(), share // per_el,
+                                                          replace=False)
+            t = t[torch.from_numpy(np.sort(idx)).to(t.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        a = t.to(torch.float32 if single else torch.float64).cpu().numpy()
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def host_cpu():
@@ -298,13 +327,21 @@ def main():
                     help="configs[4] chain: spatial extent per rank (x, y, z)")
     ap.add_argument("--chain-T", dest="chain_T", type=int, default=64,
                     help="configs[4] chain: time extent")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the side measurements, the opt-in 3M form, the "
+                         "CPU baselines, the per-launch GEMM timing passes and, at N > 1, the same "
+                         "problem on one GPU with its scale checks (a plain run sets up, warms up, "
+                         "times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's "
+                         "tNSns output) as DIR/<name>.npy")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the side measurements")
     ap.add_argument("--skip", default="",
                     help="comma-separated side measurements to skip (permute, bsr, chain, 3m, "
                          "chain_dist, redistribution, dense, skinny)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-1gpu", action="store_true",
-                    help="N > 1: skip the same global problem on rank 0's GPU alone")
+                    help="--full, N > 1: skip the same global problem on rank 0's GPU alone")
     ap.add_argument("--share-gpu", choices=["host", "rccl", "nccl"], nargs="?", const="host",
                     default=None,
                     help="rehearsal of the N>1 path on a box with fewer GPUs than ranks: ranks "
@@ -313,6 +350,9 @@ def main():
                          "group, 'nccl': the same RCCL transport under the real start-up "
                          "(init_process_group('nccl', device_id=...)) -- not a bench")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_side = args.no_cpu = args.no_1gpu = True
 
     # --gpus N is the number of ranks: without a launcher, start one (a child process, before
     # anything touches the GPU; never exec) and relay its exit code; under a launcher, its world
@@ -452,18 +492,28 @@ def main():
         # comparison point (not the headline: only a normwise error bound), and ~20 ms of MFMA
         # load right before the timed region
         side.update(form3m_bench(sb, step, flops_step))
+    if not args.full and world == 1:
+        # no side measurement has brought the GPU clocks up: ~0.5 s of the step itself first
+        # (the first launches on an idle GPU run slower: with 5 warm-up steps alone, 20 timed
+        # steps measured 1-2 % under the same steps after the side measurements)
+        t_end = time.perf_counter() + 0.5
+        while time.perf_counter() < t_end:
+            step()
+            torch.cuda.synchronize()
     progress("warm-up")
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # GEMM launches per step (one untimed step with the library's per-launch timers)
-    sb.timings_enable(True)
-    sb.timings_filter("gemm_total")
-    sb.timings_reset()
-    step()
-    torch.cuda.synchronize()
-    calls_per_step = sb.timings_get("gemm_total")[1]
-    sb.timings_enable(False)
+    calls_per_step = 1
+    if args.full:
+        # GEMM launches per step (one untimed step with the library's per-launch timers)
+        sb.timings_enable(True)
+        sb.timings_filter("gemm_total")
+        sb.timings_reset()
+        step()
+        torch.cuda.synchronize()
+        calls_per_step = sb.timings_get("gemm_total")[1]
+        sb.timings_enable(False)
     barrier()
     torch.cuda.synchronize()
     # kernel time on the library's (= torch's current) stream by HIP events.  N = 1, where a step
@@ -498,7 +548,11 @@ def main():
     clk_cycles, clk_ticks = sb.tune_get("gemm.clock_cycles"), sb.tune_get("gemm.clock_ticks")
     clk_launches = sb.tune_get("gemm.clock_launches")
     sb.tune_set("gemm.clock", 0)
-    if per_launch:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"contraction_tNSns": vr})
+    if per_launch and not args.full:
+        gemm_ms, gemm_calls = None, 0  # N > 1: the per-launch pass is K more steps (--full)
+    elif per_launch:
         progress("per-launch GEMM timing")
         sb.timings_enable(True)
         sb.timings_filter("gemm_total")
@@ -514,7 +568,7 @@ def main():
     sb.timings_filter(None)
     shader_ghz = round(clk_cycles / clk_ticks * 0.1, 4) if clk_ticks > 0 else None
     # one GEMM = the MFMA kernel launch + its split-K reduce (the reduce is part of the GEMM)
-    kernel_s = gemm_ms / max(gemm_calls, 1) / 1e3
+    kernel_s = gemm_ms / max(gemm_calls, 1) / 1e3 if gemm_ms is not None else None
 
     value = flops_step * args.steps / elapsed / 1e9  # whole-job: global flops / max-rank time
     # this rank's flops per GEMM launch (a step's GEMM is cut in T chunks when a cross-rank
@@ -525,8 +579,8 @@ def main():
     # complex MAC (8 flops); the opt-in 3-multiplication form 3 (6 flops)
     m3 = sb.tune_get("gemm.m3") > 0
     exec_per_alg = 6.0 / 8.0 if m3 else 1.0
-    algorithmic = flops_launch / kernel_s / 1e12
-    achieved = algorithmic * exec_per_alg
+    algorithmic = flops_launch / kernel_s / 1e12 if kernel_s else None
+    achieved = algorithmic * exec_per_alg if kernel_s else None
 
     # strong scaling: the same global problem on rank 0's GPU alone (outside the timed region),
     # whose output is also the answer every N > 1 result is checked against
@@ -588,6 +642,11 @@ def main():
                            "v0's partition by an all-to-all)",
                            "RCCL" if args.share_gpu != "host" else
                            "host staging"))
+        # a plain N > 1 run: a step's GEMM launches are not timed apart from its exchanges
+        no_launch_timing = {"bound": "mfma", "achieved": None, "peak": PEAK_FP64_TFLOPS,
+                            "unit": "TFLOP/s", "frac": None,
+                            "note": "the per-launch GEMM timing at N > 1 takes steps of its own: "
+                                    "--full"}
         line = {
             "metric": "lattice contraction GFLOP/s + permute GB/s, 16^4 spin×color, 1/2/4/8 GPUs",
             "value": round(value, 2),
@@ -598,6 +657,7 @@ def main():
             "comm_transport": transport["kind"],
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
             # the N > 1 lines strong-scale configs[3]; N = 1 is the single-GPU configs[1] point
@@ -615,7 +675,8 @@ def main():
                            4 * n, vol(p0[rank][1][3:]), p0[rank][1][0]),
                        "parallelism": ("xyzt grid %s" % "x".join(map(str, grid))
                                        if world > 1 else "single GPU")},
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 3),
+            "roofline": no_launch_timing if kernel_s is None else {
+                         "bound": "mfma", "achieved": round(achieved, 3),
                          "peak": PEAK_FP64_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / PEAK_FP64_TFLOPS, 4),
                          "traffic": traffic, "traffic_unit": "bytes per launch",

@@ -1,9 +1,9 @@
 """The reference's own test programs as callers of the drop-in build (shared by the golden
 generator and the tests).
 
-tests/refcallers/Makefile compiles superbblas's tests/bsr.cpp, contract.cpp, dist.cpp, blas.cpp,
-dense.cpp, storage.cpp and storage_details.cpp, unchanged and from where they lie under /root/reference, against
-include/superbblas.h and libsuperbblas_amd.so.  oracle/Makefile (`refcallers`) builds the same
+oracle/Makefile (`callers`) compiles superbblas's tests/bsr.cpp, contract.cpp, dist.cpp, blas.cpp,
+dense.cpp, storage.cpp and storage_details.cpp, unchanged and from where they lie in the
+reference's tree, against include/superbblas.h and libsuperbblas_amd.so (oracle/_ref/callers).  oracle/Makefile (`refcallers`) builds the same
 sources against the reference's own headers (CPU, OpenBLAS).  The checks the programs carry
 (bsr.cpp:287-352 exact product values at SB_DEBUG=1, contract.cpp:238-271 against a brute-force
 contraction, blas.cpp:47-63 copy_n against host loops, storage.cpp:280-351 every value read back

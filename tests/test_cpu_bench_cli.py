@@ -14,6 +14,38 @@ def test_bench_cli_contract():
         assert flag in r.stdout
 
 
+def test_bench_cli_full_and_dump_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    for flag in ("--full", "--dump-outputs"):
+        assert flag in r.stdout
+
+
+def test_dump_outputs(tmp_path):
+    """bench.dump_outputs: float64 (re, im) pairs of a complex<double> tensor, whole when it fits
+    its share of the byte cap, otherwise the same seeded sample of its elements in every run"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.complex(torch.arange(24, dtype=torch.float64), -torch.arange(24, dtype=torch.float64))
+    f = torch.arange(7, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / "a"), {"t": t, "f": f})
+    a = np.load(tmp_path / "a" / "t.npy")
+    assert a.dtype == np.float64 and a.shape == (24, 2)
+    assert np.array_equal(a[:, 0], np.arange(24)) and np.array_equal(a[:, 1], -np.arange(24))
+    b = np.load(tmp_path / "a" / "f.npy")
+    assert b.dtype == np.float32 and np.array_equal(b, np.arange(7))
+    import unittest.mock as um
+    with um.patch.object(bench, "DUMP_MAX_BYTES", 10 * 16):
+        bench.dump_outputs(str(tmp_path / "b"), {"t": t})
+        bench.dump_outputs(str(tmp_path / "c"), {"t": t})
+    s1, s2 = np.load(tmp_path / "b" / "t.npy"), np.load(tmp_path / "c" / "t.npy")
+    assert s1.shape == (10, 2) and s1.nbytes <= 10 * 16 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1[:, 0]) > 0) and np.array_equal(s1[:, 0], -s1[:, 1])
+
+
 def test_global_fill_partition_invariant():
     """bench.global_fill gives every partition (including periodic wraps) slices of one global
     tensor: the property the N > 1 scale checks rest on"""

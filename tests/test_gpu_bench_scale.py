@@ -1,4 +1,4 @@
-"""bench.py --gpus N proves its answer: every N > 1 line carries scale_check_rel_err_* fields,
+"""bench.py --full --gpus N proves its answer: every N > 1 line carries scale_check_rel_err_* fields,
 the distributed configs[3] contraction (4a), its redistributing form (4b) and the configs[4]
 chain each compared with the same global problem run on one GPU from the same global inputs.
 
@@ -28,7 +28,7 @@ def test_bench_n2_scale_check(gpu, config):
     env = dict(os.environ, OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--config", config, "--L", "8", "--ncols", "16", "--chain-L", "4", "--chain-T", "8",
            "--share-gpu", "rccl"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
@@ -50,8 +50,8 @@ def _bench_no_launcher(n, extra, timeout=420, share="rccl"):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--share-gpu",
-           share] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(n),
+           "--share-gpu", share] + extra
     # the ranks' progress lines (stderr) go to a file under gpurun_out/ when it exists, so a long
     # multi-rank run keeps showing signs of life
     outdir = os.path.join(ROOT, "gpurun_out")
@@ -101,7 +101,7 @@ def test_bench_real_startup_nccl_pg(gpu, n):
 
 
 def test_bench_scale_command_defaults(gpu):
-    """the driver's SCALE command at its defaults -- `bench.py --gpus 8`, nothing else, here with
+    """the driver's SCALE command at its defaults -- `bench.py --full --gpus 8`, nothing else, here with
     the 8 ranks sharing the test box's GPU (--share-gpu nccl: the real init_process_group("nccl")
     start-up, one RCCL host id per rank): 20 timed steps of configs[3] (32^4, n = 64, the 2x2x2x1
     grid), the 4b redistribution and redistributing contraction, and configs[4]'s full 32^3 x 64

@@ -1,9 +1,9 @@
 """The reference's own test programs, unchanged, on the HIP library (the caller-level drop-in,
 SURVEY.md section 8(b): tests/contract.cpp:215-222, dist.cpp:253-259, bsr.cpp:759-766).
 
-tests/refcallers/bin/* are superbblas's tests/{bsr,contract,dist,blas,dense}.cpp compiled against
-include/superbblas.h and linked to libsuperbblas_amd.so (tests/refcallers/Makefile, built in the
-build container from /root/reference).  Each runs its CPU-context section (host tensors mirrored
+oracle/_ref/callers/* are superbblas's tests/{bsr,contract,dist,blas,dense}.cpp compiled against
+include/superbblas.h and linked to libsuperbblas_amd.so (oracle/Makefile `callers`, built by
+build() where the reference's sources are present).  Each runs its CPU-context section (host tensors mirrored
 through the GPU) and its GPU sections; every section must print exactly the events the
 reference itself prints for the same invocation (tests/golden/refcallers.json): the same
 "Time in ..." steps, the same "Caught error: ..." lines -- including the reference's own known
@@ -21,14 +21,14 @@ from _refcallers import INVOCATIONS, STORAGE_DETAILS, STORAGE_FILES, details_key
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-BIN = os.path.join(HERE, "refcallers", "bin")
+BIN = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "callers")
 GOLDEN = json.load(open(os.path.join(HERE, "golden", "refcallers.json")))
 
 
 def _run(name, args, env, cwd=None):
     exe = os.path.join(BIN, name)
     if not os.path.exists(exe):
-        pytest.fail("%s missing: build it where /root/reference exists (make -C tests/refcallers)" % exe)
+        pytest.fail("%s missing: build it where the reference's sources are (make -C oracle callers)" % exe)
     e = dict(os.environ, OMP_NUM_THREADS="8", **env)
     e.pop("SB_TRACK_TIME", None)
     r = subprocess.run([exe] + args, capture_output=True, text=True, env=e, timeout=240, cwd=cwd)
@@ -109,7 +109,7 @@ def test_contract_strided_sample(gpu):
     import concurrent.futures
     exe = os.path.join(BIN, "contract")
     if not os.path.exists(exe):
-        pytest.fail("%s missing: build it where /root/reference exists (make -C tests/refcallers)" % exe)
+        pytest.fail("%s missing: build it where the reference's sources are (make -C oracle callers)" % exe)
     cases = list(range(11, 1327104, 2111))
     e = dict(os.environ, OMP_NUM_THREADS="2")
     e.pop("SB_TRACK_TIME", None)
@@ -152,7 +152,7 @@ def test_storage_details_program(gpu, fname, args):
     from its block hash and this library from the append order (DESIGN, storage notes)"""
     exe = os.path.join(BIN, "storage_details")
     if not os.path.exists(exe):
-        pytest.fail("%s missing: build it where /root/reference exists (make -C tests/refcallers)" % exe)
+        pytest.fail("%s missing: build it where the reference's sources are (make -C oracle callers)" % exe)
     r = subprocess.run([exe, os.path.join(HERE, "golden", fname)] + list(args), capture_output=True,
                        text=True, timeout=120)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
