@@ -111,13 +111,15 @@ int sbx_timings_report(char *buf, int len);
    Override a kernel-shape choice of the library for tuning / comparison runs.  The defaults are
    the measured winners; read a key with sbx_tune_get before changing it to
    restore it afterwards.  Keys: "gemm.m3", "gemm.splits", "gemm.max_bytes", "gemm.t48",
-   "gemm.share_ab", "gemm.loaders", "gemm.dma_spread", "gemm.skinny", "copy.nt", "copy.budget", "copy.run", "copy.max_elems", "copy.pair",
+   "gemm.share_ab", "gemm.herm" (a tensor contracted with itself: compute the upper triangle of
+   output tiles and mirror the rest; 0 = off, the default), "gemm.loaders", "gemm.dma_spread", "gemm.skinny", "copy.nt", "copy.budget", "copy.run", "copy.max_elems", "copy.pair",
    "copy.order", "copy.trans", "copy.btrans", "bsr.variant", "bsr.row_max_cols", "bsr.split_max_cols",
    "bsr.split_cw", "bsr.split_jb", "bsr.split_ilv", "bsr.kron_mfma", "bsr.kron_mfma_min_cols",
    "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.nt", "bsr.blk_pd", "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel", "dist.peer_copies",
-   "copy.last_pair", "dist.reduce_calls", "alloc.cross_stream_frees".  Unknown keys fail with an
+   "copy.last_pair", "gemm.last_herm" (tiles per batch entry the last GEMM launch mirrored instead
+   of computed; 0 = a full product), "dist.reduce_calls", "alloc.cross_stream_frees".  Unknown keys fail with an
    error. */
 int sbx_tune_set(const char *key, long long value);
 /* The box-copy kernel the library's planner picks for an N-d box copy (sizes and element strides

@@ -457,6 +457,7 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "gemm.splits") g_gemm_tune.splits = (int)value;
         else if (k == "gemm.t48") g_gemm_tune.t48 = (int)value;
         else if (k == "gemm.share_ab") g_gemm_tune.share_ab = (int)value;
+        else if (k == "gemm.herm") g_gemm_tune.herm = (int)value;
         else if (k == "gemm.frag") g_gemm_tune.frag = (int)value;
         else if (k == "gemm.dot_wgs") g_gemm_tune.dot_wgs = (int)value;
         else if (k == "gemm.frag_tall") g_gemm_tune.frag_tall = (int)value;
@@ -528,6 +529,8 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "gemm.splits") *value = g_gemm_tune.splits;
         else if (k == "gemm.t48") *value = g_gemm_tune.t48;
         else if (k == "gemm.share_ab") *value = g_gemm_tune.share_ab;
+        else if (k == "gemm.herm") *value = g_gemm_tune.herm;
+        else if (k == "gemm.last_herm") *value = g_gemm_tune.last_herm;
         else if (k == "gemm.frag") *value = g_gemm_tune.frag;
         else if (k == "gemm.dot_wgs") *value = g_gemm_tune.dot_wgs;
         else if (k == "gemm.frag_tall") *value = g_gemm_tune.frag_tall;

@@ -96,6 +96,12 @@ struct GemmKArgs {
     double alpha_re, alpha_im, beta_re, beta_im;
     int conja, conjb;
     int splits;
+    // Hermitian / symmetric output (gemm.herm; gemm_wave_kernel and gemm_dma_kernel <HERM>): A and B
+    // are the same memory with the same addressing and m == n, so C(j, i) is the conjugate (1:
+    // complex with exactly one operand conjugated) or the copy (2) of C(i, j); only the upper
+    // triangle of tiles is computed and each accumulator is also stored at its mirrored position
+    // (0 = off; in the padding before kchunk: the layout of the other fields is unchanged)
+    int herm;
     long kchunk;
     void *work;
     unsigned long long *probe; // tools only: workgroup 0 stores s_memtime / s_memrealtime at its start and end
@@ -481,8 +487,16 @@ struct NoLoader { // (LW == 0: every wave issues its share through DmaOperand)
 // and twice the workgroups fit a CU
 // LW > 0: only waves 0..LW-1 issue the slab DMA (K-major operands without split groups), each
 // spreading its share over the first SP k-steps of the slab; the other waves issue no DMA
+// HERM: Hermitian / symmetric output (p.herm; a tensor contracted with itself, m == n, square
+// tiles): the grid holds only the tiles with ti <= tj, tm (tm + 1) / 2 per batch entry and split
+// (a triangular workgroup index); a diagonal tile is computed whole, an off-diagonal tile's lanes
+// also store each accumulator, conjugated (p.herm 1) or as is (2), at its mirrored position --
+// before alpha and beta, which act on that position's own old C value -- in C or in the split-K
+// workspace.  The split-K factor, the k order and every computed element's bits are those of the
+// full product.
 template <typename R, bool CPLX, bool AK, bool BK, int BM, int BN, int BKK, int WM, int WN,
-          bool M3 = false, bool PF = false, int KG = 1, bool SH = false, int LW = 0, int SP = 1>
+          bool M3 = false, bool PF = false, int KG = 1, bool SH = false, int LW = 0, int SP = 1,
+          bool HERM = false>
 __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKArgs p) {
     typedef typename Elem<R, CPLX>::type E;
     typedef typename Mfma<R>::acc_t acc_t;
@@ -507,10 +521,24 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
     const int nwg = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
     const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    const int ti = wg % p.tm;
-    int rest = wg / p.tm;
-    const int tj = rest % p.tn;
-    rest /= p.tn;
+    static_assert(!HERM || (BM == BN && !M3 && !SH), "Hermitian output: square tiles, 4M form");
+    int ti, tj, rest;
+    if constexpr (HERM) {
+        // tile t of the upper triangle, column by column: t = tj (tj + 1) / 2 + ti, ti <= tj
+        const long ntri = (long)p.tm * (p.tm + 1) / 2;
+        const long t = wg % ntri;
+        rest = (int)(wg / ntri);
+        long c = (long)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+        while (c * (c + 1) / 2 > t) --c; // (the float root is off by a few at most)
+        while ((c + 1) * (c + 2) / 2 <= t) ++c;
+        tj = (int)c;
+        ti = (int)(t - c * (c + 1) / 2);
+    } else {
+        ti = wg % p.tm;
+        rest = wg / p.tm;
+        tj = rest % p.tn;
+        rest /= p.tn;
+    }
     const int split = rest % p.splits;
     const long bb = rest / p.splits;
     const long m0 = (long)ti * BM, n0 = (long)tj * BN;
@@ -849,6 +877,19 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
         p.probe[3 + 3 * bid] = __builtin_amdgcn_s_memrealtime();
     }
     const int ccol = lane & 15;
+    // the accumulator (vr, vi) of C(gi, gj): the result, or this split's partial
+    auto put = [&](long gi, long gj, R vr, R vi) {
+        if (p.splits == 1) {
+            R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
+            epilogue_store<R>(cptr, vr, vi, p, CPLX);
+        } else {
+            E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
+            if constexpr (CPLX)
+                *w = E{vr, vi};
+            else
+                *w = vr;
+        }
+    };
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -865,15 +906,10 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
                     vr = p1 - p2;
                     vi = acc3[i][j][r] - p1 - p2;
                 }
-                if (p.splits == 1) {
-                    R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-                    epilogue_store<R>(cptr, vr, vi, p, CPLX);
-                } else {
-                    E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-                    if constexpr (CPLX)
-                        *w = E{vr, vi};
-                    else
-                        *w = vr;
+                put(gi, gj, vr, vi);
+                if constexpr (HERM) {
+                    // an off-diagonal tile (m == n: the mirrored position is in range with this one)
+                    if (m0 != n0) put(gj, gi, vr, p.herm == 1 ? -vi : vi);
                 }
             }
 }
@@ -893,7 +929,14 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
 // (an agent-scope counter per entry, zeroed before the launch): it adds the partials of all
 // splits in split order -- the same order and arithmetic as splitk_reduce_kernel, so the result
 // does not depend on which workgroup finishes last -- and writes C; no second kernel
-template <typename R, bool CPLX, bool AK, int BM, int BKK, int KG, int RING, bool FUSE = false>
+// HERM: Hermitian / symmetric output (p.herm): no MFMA is issued for the 16 x 16 sub-tiles below
+// the diagonal (i > j: 3 of 9 at BM = 48), whose values are the mirrored accumulators of the
+// sub-tiles (j, i); the sub-tiles with i <= j see the same MFMA sequence, k partition and tree sum
+// as the full product (bit-identical).  Wave 0's lanes store each strictly-upper accumulator at
+// both positions, in C (before alpha and beta) or in the split-K workspace, so the split-K sums
+// are unchanged.
+template <typename R, bool CPLX, bool AK, int BM, int BKK, int KG, int RING, bool FUSE = false,
+          bool HERM = false>
 __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, unsigned *counters) {
     typedef typename Elem<R, CPLX>::type E;
     typedef typename Mfma<R>::acc_t acc_t;
@@ -983,6 +1026,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int j = 0; j < MT; ++j) {
+                        if (HERM && i > j) continue; // (mirrored from sub-tile (j, i))
                         accR[i][j] = Mfma<R>::mma(af[i].x, bf[j].x, accR[i][j]);
                         accI[i][j] = Mfma<R>::mma(af[i].x, bf[j].y, accI[i][j]);
                     }
@@ -990,6 +1034,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
                     for (int j = 0; j < MT; ++j) {
+                        if (HERM && i > j) continue;
                         accR[i][j] = Mfma<R>::mma(-af[i].y, bf[j].y, accR[i][j]);
                         accI[i][j] = Mfma<R>::mma(af[i].y, bf[j].x, accI[i][j]);
                     }
@@ -997,7 +1042,10 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
-                    for (int j = 0; j < MT; ++j) accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
+                    for (int j = 0; j < MT; ++j) {
+                        if (HERM && i > j) continue;
+                        accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
+                    }
             }
         }
     }
@@ -1014,6 +1062,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
                 for (int j = 0; j < MT; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
+                        if (HERM && i > j) continue; // (live sub-tiles only)
                         E v;
                         if constexpr (CPLX) v = E{accR[i][j][r], accI[i][j][r]};
                         else v = accR[i][j][r];
@@ -1028,6 +1077,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
                 for (int j = 0; j < MT; ++j)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
+                        if (HERM && i > j) continue;
                         const E v = red[((i * MT + j) * 4 + r) * 64 + lane];
                         if constexpr (CPLX) {
                             accR[i][j][r] += v.x;
@@ -1041,44 +1091,55 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
     const bool fuse = FUSE && p.splits > 1;
     if (wave != 0 && !fuse) return;
     if (wave == 0) {
+        // the accumulator (vr, vi) of C(gi, gj): the result, or this split's partial
+        auto put = [&](long gi, long gj, R vr, R vi) {
+            if (p.splits == 1) {
+                R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
+                epilogue_store<R>(cptr, vr, vi, p, CPLX);
+            } else {
+                E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
+                E v;
+                if constexpr (CPLX) v = E{vr, vi};
+                else v = vr;
+                if constexpr (FUSE) {
+                    // write-through (sc1) stores: the partial reaches memory without a
+                    // release fence (no L2 write-back)
+                    if constexpr (sizeof(E) == 8)
+                        __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, v),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else if constexpr (sizeof(E) == 4)
+                        __hip_atomic_store((unsigned *)w, __builtin_bit_cast(unsigned, v),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    else {
+                        const R re = vr, im = vi;
+                        __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, re),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store((unsigned long long *)w + 1, __builtin_bit_cast(unsigned long long, im),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                } else {
+                    *w = v;
+                }
+            }
+        };
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
             for (int j = 0; j < MT; ++j)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
+                    if (HERM && i > j) continue;
                     const long gi = 16 * i + Mfma<R>::row(lane, r);
                     const long gj = 16 * j + frow;
                     if (gi >= p.m || gj >= p.n) continue;
                     const R vr = accR[i][j][r];
                     const R vi = CPLX ? accI[i][j][r] : R(0);
-                    if (p.splits == 1) {
-                        R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-                        epilogue_store<R>(cptr, vr, vi, p, CPLX);
-                    } else {
-                        E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-                        E v;
-                        if constexpr (CPLX) v = E{vr, vi};
-                        else v = vr;
-                        if constexpr (FUSE) {
-                            // write-through (sc1) stores: the partial reaches memory without a
-                            // release fence (no L2 write-back)
-                            if constexpr (sizeof(E) == 8)
-                                __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, v),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            else if constexpr (sizeof(E) == 4)
-                                __hip_atomic_store((unsigned *)w, __builtin_bit_cast(unsigned, v),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            else {
-                                const R re = vr, im = vi;
-                                __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, re),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                __hip_atomic_store((unsigned long long *)w + 1, __builtin_bit_cast(unsigned long long, im),
-                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                        } else {
-                            *w = v;
-                        }
+                    put(gi, gj, vr, vi);
+                    if constexpr (HERM) {
+                        // a strictly-upper sub-tile also fills the mirrored position (m == n: in
+                        // range with this one) with the conjugate (p.herm 1) or the copy (2) of
+                        // the accumulator
+                        if (i < j) put(gj, gi, vr, p.herm == 1 ? -vi : vi);
                     }
                 }
     }
@@ -1487,6 +1548,29 @@ long prepare_launch(GemmKArgs &p, int BM, int BN, int BKK, long splits, long tar
     return nwg;
 }
 
+/// A and B are the same memory with the same M / N and K addressing, and m == n
+bool same_operands(const GemmKArgs &p) {
+    return p.a == p.b && p.m == p.n && p.sa_m == p.sb_n && p.sa_k == p.sb_k && p.sa_b == p.sb_b &&
+           p.m_lo == p.n_lo && p.sa_m_hi == p.sb_n_hi && p.sa_k_hi == p.sb_k_hi;
+}
+
+/// Hermitian-output mode of a launch (after prepare_launch: p.a_bytes), the GemmKArgs::herm of
+/// the <HERM> kernels: 0 (the full product) unless gemm.herm is set, A and B are the same operand
+/// and C lies apart from it; else 1 when C(j, i) = conj(C(i, j)) (complex, exactly one operand
+/// conjugated) or 2 when C(j, i) = C(i, j) (real types, complex symmetric)
+template <typename E> int herm_mode(const GemmKArgs &p, bool cplx) {
+    if (!g_gemm_tune.herm || !same_operands(p)) return 0;
+    if (p.sc_m < 0 || p.sc_n < 0 || p.sc_b < 0 || p.sc_m_hi < 0 || p.sc_n_hi < 0 || p.sa_b < 0)
+        return 0;
+    auto ext = [](long n, long lo, long st, long st_hi) { return (n / lo - 1) * st_hi + (lo - 1) * st; };
+    const long ec = p.split ? ext(p.m, p.m_lo, p.sc_m, p.sc_m_hi) + ext(p.n, p.n_lo, p.sc_n, p.sc_n_hi)
+                            : (p.m - 1) * p.sc_m + (p.n - 1) * p.sc_n;
+    const char *c0 = (const char *)p.c, *c1 = c0 + ((p.batch - 1) * p.sc_b + ec + 1) * (long)sizeof(E);
+    const char *a0 = (const char *)p.a, *a1 = a0 + (p.batch - 1) * p.sa_b * (long)sizeof(E) + p.a_bytes;
+    if (c0 < a1 && a0 < c1) return 0; // C aliases A
+    return cplx && (p.conja != 0) != (p.conjb != 0) ? 1 : 2;
+}
+
 template <typename R, bool CPLX>
 void launch_reduce(const GemmKArgs &p, hipStream_t stream) {
     if (p.splits <= 1) return;
@@ -1549,8 +1633,11 @@ void clock_read_impl(int device, unsigned long long out[3], bool reset) {
 }
 
 /// Launch one tile configuration of the LDS-DMA kernel
+/// (HERM_OK: the configuration has a Hermitian-output instantiation for launches with several
+/// tiles, see herm_mode)
 template <typename R, bool CPLX, bool AK, bool BK, int BM, int BN, int BKK, int WM, int WN,
-          bool ALLOW_M3 = true, bool PF = false, int KG = 1, bool SH = false, int LW = 0, int SP = 1>
+          bool ALLOW_M3 = true, bool PF = false, int KG = 1, bool SH = false, int LW = 0, int SP = 1,
+          bool HERM_OK = false>
 void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long splits = 0,
                     long target_wgs = 1024) {
     // complex: the 4-multiplication form unless the 3-multiplication form is asked for (config
@@ -1561,13 +1648,21 @@ void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long sp
     Scratch work;
     if (g_gemm_tune.splits > 0) splits = g_gemm_tune.splits;
     p.dma_nt = g_gemm_tune.dma_nt;
-    p.same_ab = g_gemm_tune.share_ab && p.a == p.b && p.m == p.n && p.sa_m == p.sb_n &&
-                p.sa_k == p.sb_k && p.sa_b == p.sb_b && p.m_lo == p.n_lo &&
-                p.sa_m_hi == p.sb_n_hi && p.sa_k_hi == p.sb_k_hi;
-    const long nwg = prepare_launch<typename Elem<R, CPLX>::type>(p, BM, BN, BKK, splits,
-                                                                   target_wgs, work, device);
+    p.same_ab = g_gemm_tune.share_ab && same_operands(p);
+    long nwg = prepare_launch<typename Elem<R, CPLX>::type>(p, BM, BN, BKK, splits, target_wgs,
+                                                            work, device);
     if (SH && !(p.same_ab && p.tm == 1 && p.tn == 1))
         throw Error("gemm: internal error, shared slab image for a launch with off-diagonal tiles");
+    // Hermitian output: the upper triangle of tiles only, the split-K factor (and so the k
+    // partition of every computed element) that of the full grid
+    static_assert(!HERM_OK || (AK == BK && BM == BN && !PF && KG == 1 && !SH), "Hermitian output");
+    if constexpr (HERM_OK) {
+        if (!m3 && p.tm > 1) p.herm = herm_mode<typename Elem<R, CPLX>::type>(p, CPLX);
+        if (p.herm) {
+            nwg = (long)p.tm * (p.tm + 1) / 2 * p.batch * p.splits;
+            g_gemm_tune.last_herm = p.tm * (p.tm - 1) / 2;
+        }
+    }
     if (unsigned long long *meter = gemm_clock_meter(device)) {
         p.probe = meter;
         p.probe_all = -1;
@@ -1575,7 +1670,16 @@ void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long sp
     KernelTimer total("gemm_total", stream);
     {
         KernelTimer timer("gemm", stream);
-        if constexpr (ALLOW_M3) {
+        bool launched = false;
+        if constexpr (HERM_OK) {
+            if (p.herm) {
+                hipLaunchKernelGGL((gemm_dma_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN, false, PF, KG, SH, LW, SP, true>),
+                                   dim3((unsigned)nwg), dim3(WM * WN * KG * 64), 0, stream, p);
+                launched = true;
+            }
+        }
+        if (launched) {
+        } else if constexpr (ALLOW_M3) {
             if (m3)
                 hipLaunchKernelGGL((gemm_dma_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN, CPLX>),
                                    dim3((unsigned)nwg), dim3(WM * WN * 64), 0, stream, p);
@@ -1626,11 +1730,19 @@ void launch_wave_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long t
     if (p.tm != 1 || p.tn != 1 || p.m != p.n)
         throw Error("gemm: internal error, wave kernel for a launch with several tiles");
     unsigned *counters = FUSE && p.splits > 1 ? splitk_counters(stream, p.batch, device) : nullptr;
+    // Hermitian output: the same grid and split-K workspace, no MFMAs below the diagonal
+    constexpr int MT = BM / 16;
+    p.herm = MT > 1 ? herm_mode<typename Elem<R, CPLX>::type>(p, CPLX) : 0;
+    if (p.herm) g_gemm_tune.last_herm = MT * (MT - 1) / 2;
     KernelTimer total("gemm_total", stream);
     {
         KernelTimer timer("gemm", stream);
-        hipLaunchKernelGGL((gemm_wave_kernel<R, CPLX, AK, BM, BKK, KG, RING, FUSE>),
-                           dim3((unsigned)nwg), dim3(KG * 64), 0, stream, p, counters);
+        if (p.herm)
+            hipLaunchKernelGGL((gemm_wave_kernel<R, CPLX, AK, BM, BKK, KG, RING, FUSE, true>),
+                               dim3((unsigned)nwg), dim3(KG * 64), 0, stream, p, counters);
+        else
+            hipLaunchKernelGGL((gemm_wave_kernel<R, CPLX, AK, BM, BKK, KG, RING, FUSE>),
+                               dim3((unsigned)nwg), dim3(KG * 64), 0, stream, p, counters);
         SBX_HIP_CHECK(hipGetLastError());
     }
     if (!FUSE) launch_reduce<R, CPLX>(p, stream);
@@ -1664,6 +1776,9 @@ void launch_tiled(const GemmKArgs &p, int device, hipStream_t stream) {
     // output is large enough, else 64x64 (tools/gemm_tune.hip: 67.5 / 65.5 TFLOP/s on the
     // 16^4 lattice contraction, 86 % / 83 % of the 78.6 TFLOP/s FP64 matrix peak)
     typedef typename Elem<R, CPLX>::type E;
+    // the Hermitian-output instantiations (gemm.herm): the 128x128 and 64x64 forms the library
+    // picks by itself, for operands laid out alike (a tensor contracted with itself)
+    constexpr bool HM = AK == BK;
     if (!dma_ok<E>(p, AK, BK)) {
         launch_tiled_cfg<R, CPLX, AK, BK, 64, 64, 16, 2, 2>(p, device, stream);
     } else if constexpr (std::is_same<R, double>::value && CPLX) {
@@ -1693,15 +1808,15 @@ void launch_tiled(const GemmKArgs &p, int device, hipStream_t stream) {
                 else if (lw == 8 && sp == 0)
                     launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 8, 0>(p, device, stream, 0, 256);
                 else if (lw == 8)
-                    launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 8, 1>(p, device, stream, 0, 256);
+                    launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 8, 1, true>(p, device, stream, 0, 256);
                 else if (lw == 16 && sp == 4)
                     launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 16, 4>(p, device, stream, 0, 256);
                 else
-                    launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false>(p, device, stream, 0, 256);
+                    launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 0, 1, HM>(p, device, stream, 0, 256);
             } else
-                launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false>(p, device, stream, 0, 256);
+                launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 0, 1, HM>(p, device, stream, 0, 256);
         } else {
-            launch_dma_cfg<R, CPLX, AK, BK, 64, 64, 8, 2, 2>(p, device, stream, 0, 1024);
+            launch_dma_cfg<R, CPLX, AK, BK, 64, 64, 8, 2, 2, true, false, 1, false, 0, 1, HM>(p, device, stream, 0, 1024);
         }
     } else {
         // small outputs (33..48 rows and columns, e.g. the chain's TSnsN contraction: m = n = 4 x
@@ -1723,9 +1838,7 @@ void launch_tiled(const GemmKArgs &p, int device, hipStream_t stream) {
             // a tensor contracted with itself, one tile per batch entry (the chain's y^H y):
             // wave-private slab rings, A-only images (tools/chain_contraction.py, round 4: 0.167 ->
             // 0.142-0.146 ms warm against the t48 = 4 form, profiles/r04_chain_gemm.txt)
-            const bool sh = g_gemm_tune.share_ab && p.a == p.b && p.m == p.n && p.sa_m == p.sb_n &&
-                            p.sa_k == p.sb_k && p.sa_b == p.sb_b && p.m_lo == p.n_lo &&
-                            p.sa_m_hi == p.sb_n_hi && p.sa_k_hi == p.sb_k_hi;
+            const bool sh = g_gemm_tune.share_ab && same_operands(p);
             if constexpr (!AK && !BK && sizeof(E) >= 8) {
                 // (comparison forms: 13 four waves per workgroup, 1024 workgroups; 14 the same with
                 // 16-deep slabs; 16 sixteen waves, 256 workgroups)
@@ -1747,9 +1860,9 @@ void launch_tiled(const GemmKArgs &p, int device, hipStream_t stream) {
         // 8-byte and 4-byte elements: 32-deep slabs (fewer barriers per MFMA; measured against
         // 16 and 64 on the lattice shape: double 50.5, complex<float> 116, float 107 TFLOP/s)
         if (p.m >= 128 && p.n >= 128)
-            launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 32, 4, 2>(p, device, stream, 0, 256);
+            launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 32, 4, 2, true, false, 1, false, 0, 1, HM>(p, device, stream, 0, 256);
         else
-            launch_dma_cfg<R, CPLX, AK, BK, 64, 64, 32, 2, 2>(p, device, stream, 0, 1024);
+            launch_dma_cfg<R, CPLX, AK, BK, 64, 64, 32, 2, 2, true, false, 1, false, 0, 1, HM>(p, device, stream, 0, 1024);
     }
 }
 
@@ -2070,6 +2183,7 @@ void launch_gemm(const GemmDesc &d, int device) {
     set_device(device);
     hipStream_t s = get_stream(device);
     GemmKArgs p = make_args(d);
+    g_gemm_tune.last_herm = 0; // (set by the launchers of the Hermitian-output kernels)
     const bool scale_only = (d.k == 0 || (p.alpha_re == 0 && p.alpha_im == 0));
     switch (d.t) {
     case SBX_CDOUBLE:

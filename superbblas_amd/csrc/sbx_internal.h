@@ -243,6 +243,15 @@ struct GemmTune {
                  ///< choice: wave rings of 8 waves, 8-deep slabs, for a tensor contracted with
                  ///< itself, else k-group workgroups)
     int share_ab = 1; ///< LDS-DMA kernel: one slab image for A and B when they are the same memory (0 = off)
+    int herm = 0; ///< a tensor contracted with itself (A and B the same memory and addressing, m == n, C apart
+                  ///< from it) on the wave-ring kernel or on several 128x128 / 64x64 LDS-DMA tiles: != 0
+                  ///< computes the upper triangle of (sub-)tiles only and stores each accumulator, conjugated
+                  ///< for a Hermitian output, at its mirrored position too (0 = the full product, the default:
+                  ///< a mirrored imaginary part is the exact conjugate of its partner, not the bits of the
+                  ///< full product)
+    std::atomic<int> last_herm{0}; ///< read-back ("gemm.last_herm"): the tiles per batch entry the last GEMM
+                                   ///< launch mirrored instead of computed -- 16x16 sub-tiles on the wave-ring
+                                   ///< kernel, BM x BN tiles on the LDS-DMA kernel; 0 = a full product
     int loaders = 8; ///< complex<double> 128x128 LDS-DMA kernel, K-major operands: only this many waves
                      ///< (4, 8, 16) issue the slab DMA (0 = every wave its share); config 2: 1.491 ->
                      ///< 1.475 ms at 4 or 8 (tools/studies/gemm_loaders.py, profiles/r05_gemm_loaders.txt)
