@@ -119,7 +119,9 @@ int sbx_timings_report(char *buf, int len);
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel", "dist.peer_copies",
    "copy.last_pair", "gemm.last_herm" (tiles per batch entry the last GEMM launch mirrored instead
-   of computed; 0 = a full product), "dist.reduce_calls", "alloc.cross_stream_frees".  Unknown keys fail with an
+   of computed; 0 = a full product), "gemm.last_lean" (1 when the last GEMM launch took the lean form of
+   the complex<double> 128x128x16 kernel, key "gemm.lean", on by default and bit-identical to the generic
+   form), "dist.reduce_calls", "alloc.cross_stream_frees".  Unknown keys fail with an
    error. */
 int sbx_tune_set(const char *key, long long value);
 /* The box-copy kernel the library's planner picks for an N-d box copy (sizes and element strides

@@ -433,6 +433,7 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "gemm.loaders") g_gemm_tune.loaders = (int)value;
         else if (k == "gemm.dma_spread") g_gemm_tune.dma_spread = (int)value;
         else if (k == "gemm.dma_nt") g_gemm_tune.dma_nt = (int)value;
+        else if (k == "gemm.lean") g_gemm_tune.lean = (int)value;
         else if (k == "gemm.skinny") g_gemm_tune.skinny = (int)value;
         else if (k == "bsr.variant") g_bsr_tune.variant = (int)value;
         else if (k == "bsr.row_max_cols") g_bsr_tune.row_max_cols = (long)value;
@@ -504,6 +505,8 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "gemm.loaders") *value = g_gemm_tune.loaders;
         else if (k == "gemm.dma_spread") *value = g_gemm_tune.dma_spread;
         else if (k == "gemm.dma_nt") *value = g_gemm_tune.dma_nt;
+        else if (k == "gemm.lean") *value = g_gemm_tune.lean;
+        else if (k == "gemm.last_lean") *value = g_gemm_tune.last_lean;
         else if (k == "gemm.skinny") *value = g_gemm_tune.skinny;
         else if (k == "bsr.variant") *value = g_bsr_tune.variant;
         else if (k == "bsr.row_max_cols") *value = g_bsr_tune.row_max_cols;

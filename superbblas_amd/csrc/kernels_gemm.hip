@@ -915,6 +915,217 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
 }
 
 // ---------------------------------------------------------------------------------------------
+// Lean form of gemm_dma_kernel<double, true, true, true, 128, 128, 16, 4, 4, ..., LW = 8, SP = 1>
+// (complex<double>, K-major operands, 8 loader waves) for launches that need none of its
+// generality (lean_eligible: whole 128 x 128 tiles, whole 16-deep slabs, no split groups, no shared
+// slab image, default DMA policy).  The tile numbering, the slab image, the k order and partition,
+// the MFMA chain of every accumulator and the epilogue are gemm_dma_kernel's, so every output bit
+// is; what is gone is the per-piece bookkeeping of the main loop:
+//  * every DMA piece is in range: a loader lane's source offsets are computed once (one VGPR per
+//    piece), the slab's k offset is the instruction's scalar offset (one s_add per slab and
+//    operand), the LDS destination is m0 = a scalar base that flips with the buffer + a literal;
+//  * a 32-bit slab counter;
+//  * conjugation is a template parameter and the signs of the four real products are the MFMA's
+//    neg modifier (an exact sign flip of the A operand, as the xor of the generic form): no VALU
+//    work on the fragments at all;
+//  * split-K partials leave through LDS as whole column runs (see the epilogue).
+// ---------------------------------------------------------------------------------------------
+template <int NEG>
+__device__ __forceinline__ Mfma<double>::acc_t mma_f64(double a, double b, Mfma<double>::acc_t c) {
+    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, NEG); // (f64: blgp is neg:[A,B,C])
+}
+
+/// One 64-lane LDS-DMA piece: 16 bytes per lane from rs + voff + soff to LDS sbase + OFF + 16 lane
+template <int OFF>
+__device__ __forceinline__ void lean_dma_piece(unsigned voff, unsigned sbase,
+                                               __amdgpu_buffer_rsrc_t rs, unsigned soff) {
+    asm volatile("s_add_u32 m0, %1, %4\n\t"
+                 "s_nop 0\n\t"
+                 "buffer_load_dwordx4 %0, %2, %3 offen lds"
+                 :
+                 : "v"(voff), "s"(sbase), "s"(rs), "s"(soff), "n"(OFF)
+                 : "memory", "m0", "scc");
+}
+
+template <bool CA, bool CB>
+__global__ void __launch_bounds__(1024) gemm_lean_kernel(const GemmKArgs p) {
+    typedef double R;
+    typedef double2 E;
+    typedef Mfma<R>::acc_t acc_t;
+    constexpr int BM = 128, BN = 128, BKK = 16, WN = 4, WTM = 32, WTN = 32, MT = 2, NT = 2;
+    constexpr int ES = 16, LW = 8, NI = 4, RSTEP = 32; // 512 loader lanes, 4 pieces per operand
+    constexpr int SLAB = (BM + BN) * BKK;              // elements per slab (A then B)
+    constexpr unsigned IMG_B = BM * BKK * ES, SLAB_B = SLAB * ES, PIECE_B = LW * 64 * 16;
+    typedef DmaOperand<true, BM, BKK, 1024, ES> Op; // (the slab image: slot())
+    __shared__ __attribute__((aligned(16))) E lds[2 * SLAB];
+
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
+    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int ti = wg % p.tm;
+    int rest = wg / p.tm;
+    const int tj = rest % p.tn;
+    rest /= p.tn;
+    const int split = rest % p.splits;
+    const long bb = rest / p.splits;
+    const long m0 = (long)ti * BM, n0 = (long)tj * BN;
+    const long k_begin = (long)split * p.kchunk;
+    const long k_end = min(p.k, k_begin + p.kchunk);
+
+    const E *A = (const E *)p.a + bb * p.sa_b;
+    const E *B = (const E *)p.b + bb * p.sb_b;
+    const __amdgpu_buffer_rsrc_t rsA =
+        __builtin_amdgcn_make_buffer_rsrc((void *)A, (short)0, (int)p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsB =
+        __builtin_amdgcn_make_buffer_rsrc((void *)B, (short)0, (int)p.b_bytes, 0x00020000);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned long long clk0 = 0, rt0 = 0;
+    if (p.probe && bid == 0) {
+        clk0 = __builtin_amdgcn_s_memtime();
+        rt0 = __builtin_amdgcn_s_memrealtime();
+    }
+    // loader lanes (DmaRowsK's map): granule slot tid + 512 i is row tid / 16 + 32 i, swizzled
+    // column (tid % 16) ^ (row & 15)
+    const bool loader = wave < LW;
+    unsigned va[NI], vb[NI];
+    {
+        const int r = tid >> 4, k = (tid & 15) ^ (r & 15);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            va[i] = (unsigned)(((m0 + r + RSTEP * i) * p.sa_m + (long)k * p.sa_k) * ES);
+            vb[i] = (unsigned)(((n0 + r + RSTEP * i) * p.sb_n + (long)k * p.sb_k) * ES);
+        }
+    }
+    unsigned ka = (unsigned)(k_begin * p.sa_k * ES), kb = (unsigned)(k_begin * p.sb_k * ES);
+    const unsigned ka_step = (unsigned)(BKK * p.sa_k * ES), kb_step = (unsigned)(BKK * p.sb_k * ES);
+    const unsigned lbase = lds_addr(lds) + (unsigned)wave * (64 * 16);
+    // the 8 pieces of a slab (A's four, then B's) into the image at LDS `sb`
+    auto issue = [&](unsigned sb) {
+        lean_dma_piece<0 * PIECE_B>(va[0], sb, rsA, ka);
+        lean_dma_piece<1 * PIECE_B>(va[1], sb, rsA, ka);
+        lean_dma_piece<2 * PIECE_B>(va[2], sb, rsA, ka);
+        lean_dma_piece<3 * PIECE_B>(va[3], sb, rsA, ka);
+        lean_dma_piece<IMG_B + 0 * PIECE_B>(vb[0], sb, rsB, kb);
+        lean_dma_piece<IMG_B + 1 * PIECE_B>(vb[1], sb, rsB, kb);
+        lean_dma_piece<IMG_B + 2 * PIECE_B>(vb[2], sb, rsB, kb);
+        lean_dma_piece<IMG_B + 3 * PIECE_B>(vb[3], sb, rsB, kb);
+    };
+
+    const int wm = wave / WN, wn = wave % WN;
+    const int frow = wm * WTM + (lane & 15), fcol = wn * WTN + (lane & 15), kq = lane >> 4;
+    // fragment element (row, kk + kq) of the image, per k-step (the swizzle is an xor of the k-step)
+    int fa[BKK / 4], fb[BKK / 4];
+#pragma unroll
+    for (int s = 0; s < BKK / 4; ++s) {
+        fa[s] = Op::slot(frow, 4 * s + kq);
+        fb[s] = BM * BKK + Op::slot(fcol, 4 * s + kq);
+    }
+
+    acc_t accR[MT][NT], accI[MT][NT];
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            accR[i][j] = acc_t{0, 0, 0, 0};
+            accI[i][j] = acc_t{0, 0, 0, 0};
+        }
+
+    const int nslab = (int)((k_end - k_begin) / BKK); // (whole slabs)
+    if (nslab > 0 && loader) issue(lbase);
+    for (int s = 0; s < nslab; ++s) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's DMA of slab s landed
+        __syncthreads(); // ... and every wave's; the other buffer is free again
+        const int cur = s & 1;
+        ka += ka_step;
+        kb += kb_step;
+        // the whole next slab right after the barrier, ahead of the first fragment reads (spread
+        // over the first k-steps it is slower here, profiles/gemm_lean_measure.txt)
+        if (loader && s + 1 < nslab) issue(lbase + (unsigned)(cur ^ 1) * SLAB_B);
+        const E *L = lds + cur * SLAB;
+#pragma unroll
+        for (int ks = 0; ks < BKK / 4; ++ks) {
+            E af[MT], bf[NT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) af[i] = L[fa[ks] + 16 * i * BKK];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) bf[j] = L[fb[ks] + 16 * j * BKK];
+            // re += ar br - (ca ai) (cb bi), im += ar (cb bi) + (ca ai) br; ca, cb = -1 if conjugated
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    accR[i][j] = mma_f64<0>(af[i].x, bf[j].x, accR[i][j]);
+                    accI[i][j] = mma_f64<CB ? 1 : 0>(af[i].x, bf[j].y, accI[i][j]);
+                }
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    accR[i][j] = mma_f64<CA == CB ? 1 : 0>(af[i].y, bf[j].y, accR[i][j]);
+                    accI[i][j] = mma_f64<CA ? 1 : 0>(af[i].y, bf[j].x, accI[i][j]);
+                }
+        }
+    }
+
+    if (p.probe && bid == 0 && tid == 0) {
+        const unsigned long long clk1 = __builtin_amdgcn_s_memtime();
+        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+        if (p.probe_all < 0) { // the library's clock meter, as in gemm_dma_kernel
+            atomicAdd(&p.probe[0], clk1 - clk0);
+            atomicAdd(&p.probe[1], rt1 - rt0);
+            atomicAdd(&p.probe[2], 1ull);
+        } else {
+            p.probe[0] = clk1 - clk0;
+            p.probe[1] = rt1 - rt0;
+        }
+    }
+    const int ccol = lane & 15;
+    if (p.splits > 1) {
+        // split-K partials through LDS (free by now), half a tile (64 columns of 128 rows, 128 KB)
+        // at a time: a wave's store is 1 KB of one workspace column instead of 64-byte pieces of 16
+        // columns (the 16-B row slot xor-ed with the column: conflict-free 8-lane write and
+        // 16-lane read groups); the workspace layout and every bit are the generic kernel's
+        E *const w0 = (E *)p.work + (((long)split * p.batch + bb) * p.n + n0) * p.m + m0;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            __syncthreads(); // the slab buffers / the previous half are read
+            if ((wn >> 1) == half) {
+#pragma unroll
+                for (int i = 0; i < MT; ++i)
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = wm * WTM + 16 * i + Mfma<R>::row(lane, r);
+                            const int col = (wn & 1) * WTN + 16 * j + ccol;
+                            lds[col * BM + (row ^ (col & 7))] = E{accR[i][j][r], accI[i][j][r]};
+                        }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int pass = 0; pass < 64 * BM / 1024; ++pass) {
+                const int idx = pass * 1024 + tid, col = idx / BM, row = idx % BM;
+                w0[(long)(half * 64 + col) * p.m + row] = lds[col * BM + (row ^ (col & 7))];
+            }
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long gi = m0 + wm * WTM + 16 * i + Mfma<R>::row(lane, r);
+                const long gj = n0 + wn * WTN + 16 * j + ccol;
+                R *cptr = (R *)((E *)p.c + bb * p.sc_b + gi * p.sc_m + gj * p.sc_n);
+                epilogue_store<R>(cptr, accR[i][j][r], accI[i][j][r], p, true);
+            }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Wave-private slabs, for a tensor contracted with itself with one output tile per batch entry
 // (same_ab, m = n <= BM: the chain's y^H y correlator, TSnsN with m = n = 48).  Every wave of the
 // workgroup owns the whole BM x BM tile over its own contiguous part of the workgroup's k-chunk
@@ -1694,6 +1905,45 @@ void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long sp
     launch_reduce<R, CPLX>(p, stream);
 }
 
+/// A complex<double> K-major launch that gemm_lean_kernel can take in place of the 128x128x16
+/// loader-wave kernel (gemm.lean): whole tiles and whole 16-deep slabs in every split's k range
+/// (the chunks are slab multiples, prepare_launch), no split groups, no slab image shared by A and
+/// B, no Hermitian output, the 4-multiplication form and the default DMA policy
+bool lean_eligible(const GemmKArgs &p) {
+    if (!g_gemm_tune.lean || g_gemm_tune.m3 > 0 || g_gemm_tune.dma_nt || p.split) return false;
+    if (p.m % 128 || p.n % 128 || p.k % 16) return false;
+    if ((g_gemm_tune.share_ab || g_gemm_tune.herm) && same_operands(p)) return false;
+    return !(p.probe && p.probe_all > 0); // (tools: per-workgroup time stamps)
+}
+
+/// Launch gemm_lean_kernel (the grid, split-K factor and workspace of the kernel it stands in for)
+void launch_lean(const GemmKArgs &p0, int device, hipStream_t stream) {
+    GemmKArgs p = p0;
+    Scratch work;
+    const long nwg = prepare_launch<double2>(p, 128, 128, 16, g_gemm_tune.splits > 0 ? g_gemm_tune.splits : 0,
+                                             256, work, device);
+    if (unsigned long long *meter = gemm_clock_meter(device)) {
+        p.probe = meter;
+        p.probe_all = -1;
+    }
+    g_gemm_tune.last_lean = 1;
+    KernelTimer total("gemm_total", stream);
+    {
+        KernelTimer timer("gemm", stream);
+        const dim3 grid((unsigned)nwg), block(1024);
+        if (p.conja && p.conjb)
+            hipLaunchKernelGGL((gemm_lean_kernel<true, true>), grid, block, 0, stream, p);
+        else if (p.conja)
+            hipLaunchKernelGGL((gemm_lean_kernel<true, false>), grid, block, 0, stream, p);
+        else if (p.conjb)
+            hipLaunchKernelGGL((gemm_lean_kernel<false, true>), grid, block, 0, stream, p);
+        else
+            hipLaunchKernelGGL((gemm_lean_kernel<false, false>), grid, block, 0, stream, p);
+        SBX_HIP_CHECK(hipGetLastError());
+    }
+    launch_reduce<double, true>(p, stream);
+}
+
 /// The fused split-K sums' per-batch-entry counters of a stream: zero when allocated and left zero
 /// by every launch (the last workgroup of an entry resets its counter), so no memset per call;
 /// one array per stream, so launches on different streams never share a counter
@@ -1799,7 +2049,10 @@ void launch_tiled(const GemmKArgs &p, int device, hipStream_t stream) {
                 // loader waves (gemm.loaders / gemm.dma_spread, K-major operands without split
                 // groups): only waves 0..LW-1 issue the slab DMA
                 const int lw = p.split ? 0 : g_gemm_tune.loaders, sp = g_gemm_tune.dma_spread;
-                if (lw == 4 && sp == 4)
+                if (lw == 8 && sp == 1 && lean_eligible(p))
+                    // (the default form without the generic main loop's bookkeeping, gemm.lean)
+                    launch_lean(p, device, stream);
+                else if (lw == 4 && sp == 4)
                     launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 4, 4>(p, device, stream, 0, 256);
                 else if (lw == 4)
                     launch_dma_cfg<R, CPLX, AK, BK, 128, 128, 16, 4, 4, false, false, 1, false, 4, 1>(p, device, stream, 0, 256);
@@ -2184,6 +2437,7 @@ void launch_gemm(const GemmDesc &d, int device) {
     hipStream_t s = get_stream(device);
     GemmKArgs p = make_args(d);
     g_gemm_tune.last_herm = 0; // (set by the launchers of the Hermitian-output kernels)
+    g_gemm_tune.last_lean = 0; // (set by launch_lean)
     const bool scale_only = (d.k == 0 || (p.alpha_re == 0 && p.alpha_im == 0));
     switch (d.t) {
     case SBX_CDOUBLE:

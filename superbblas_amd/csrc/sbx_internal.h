@@ -259,6 +259,13 @@ struct GemmTune {
                         ///< loaders): the early barrier -- a slab's barrier before its last k-step,
                         ///< whose fragments are already read, the next slab's first ones read after it
     int dma_nt = 0;     ///< ... with the non-temporal policy (0 = the default policy)
+    int lean = 1; ///< ... at the default loaders / dma_spread: launches of whole 128x128 tiles and whole
+                  ///< 16-deep slabs (lean_eligible, kernels_gemm.hip) on gemm_lean_kernel, the same
+                  ///< arithmetic and bits without the generic main loop's bookkeeping, split-K partials
+                  ///< stored as whole column runs (0 = the generic kernel); config 2: 1.461 -> 1.39 ms
+                  ///< (tools/studies/gemm_lean.py, profiles/gemm_lean_measure.txt)
+    std::atomic<int> last_lean{0}; ///< read-back ("gemm.last_lean"): 1 when the last GEMM launch took
+                                   ///< gemm_lean_kernel, else 0
     int skinny = 1; ///< outputs with a dimension of <= 4 (and <= 16 with a short k): the dot / rows
                     ///< kernels instead of MFMA tiles (0 = off)
     int clock = 0; ///< LDS-DMA kernel clock meter (gemm_clock_meter, kernels_gemm.hip; 0 = off)
