@@ -155,6 +155,241 @@ __device__ __forceinline__ void epilogue_store(R *cptr, R vr, R vi, const GemmKA
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Helpers shared by the kernels below: the tile numbering, the operands' buffer descriptors, the
+// conjugation mask, the MFMA step of a fragment pair, the store of an accumulator, the sums
+// through LDS and over the splits, and the clock probe exist once, here.  A kernel that needs one
+// of them calls it, so the kernels agree in these by construction (every function is inlined: the
+// kernels compile to the instructions of the hand-expanded forms, tools/gemm_isa_summary.py).
+// ---------------------------------------------------------------------------------------------
+
+/// XCD-aware remap: consecutive logical workgroups share an XCD (bijective form)
+__device__ __forceinline__ int xcd_workgroup() {
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
+    return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+}
+
+/// The k range of k-split `split`
+struct KRange {
+    long begin, end;
+};
+__device__ __forceinline__ KRange split_k_range(const GemmKArgs &p, int split) {
+    const long k_begin = (long)split * p.kchunk;
+    return KRange{k_begin, min(p.k, k_begin + p.kchunk)};
+}
+
+/// The work of one workgroup: tile (ti, tj) at (m0, n0) of batch entry bb, over the k range
+/// [k_begin, k_end) of k-split `split`
+struct Tile {
+    int ti, tj, split;
+    long bb, m0, n0, k_begin, k_end;
+    // `rest` = split + splits * batch entry, once (ti, tj) are taken off the workgroup number
+    __device__ __forceinline__ void finish(const GemmKArgs &p, int rest, int BM, int BN) {
+        split = rest % p.splits;
+        bb = rest / p.splits;
+        m0 = (long)ti * BM, n0 = (long)tj * BN;
+        const KRange kr = split_k_range(p, split);
+        k_begin = kr.begin, k_end = kr.end;
+    }
+};
+/// Tile of logical workgroup wg, ti fastest, then tj, the split and the batch entry
+__device__ __forceinline__ Tile tile_of(const GemmKArgs &p, int wg, int BM, int BN) {
+    Tile t;
+    t.ti = wg % p.tm;
+    int rest = wg / p.tm;
+    t.tj = rest % p.tn;
+    t.finish(p, rest / p.tn, BM, BN);
+    return t;
+}
+/// Tile of logical workgroup wg of a Hermitian-output grid (p.herm, tm == tn): tile t of the upper
+/// triangle, column by column: t = tj (tj + 1) / 2 + ti, ti <= tj
+__device__ __forceinline__ Tile upper_tile_of(const GemmKArgs &p, int wg, int BM) {
+    Tile t;
+    const long ntri = (long)p.tm * (p.tm + 1) / 2;
+    const long tt = wg % ntri;
+    long c = (long)((__fsqrt_rn(8.f * (float)tt + 1.f) - 1.f) * 0.5f);
+    while (c * (c + 1) / 2 > tt) --c; // (the float root is off by a few at most)
+    while ((c + 1) * (c + 2) / 2 <= tt) ++c;
+    t.tj = (int)c;
+    t.ti = (int)(tt - c * (c + 1) / 2);
+    t.finish(p, (int)(wg / ntri), BM, BM);
+    return t;
+}
+
+/// Wave-uniform buffer descriptor of batch entry bb of an operand (T8/T20 of the CDNA guide)
+template <typename E>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t operand_rsrc(const void *base, long bb, long s_b,
+                                                               unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *)((const E *)base + bb * s_b), (short)0,
+                                             (int)bytes, 0x00020000);
+}
+
+/// Conjugation of the operands' fragments: the imaginary parts' sign bit flipped with an integer
+/// xor (no FP64 multiply)
+template <typename R> struct ConjMask {
+    typedef typename std::conditional<sizeof(R) == 8, unsigned long long, unsigned>::type U;
+    U ma, mb; // the sign bit where A (B) is conjugated, else 0
+    __device__ __forceinline__ ConjMask(const GemmKArgs &p) {
+        const U sign = (U)1 << (sizeof(R) * 8 - 1);
+        ma = p.conja ? sign : 0, mb = p.conjb ? sign : 0;
+    }
+    static __device__ __forceinline__ R flip(R v, U m) {
+        return __builtin_bit_cast(R, __builtin_bit_cast(U, v) ^ m);
+    }
+    // a pair of complex fragments as the MFMA step takes them
+    template <typename E, int MT, int NT>
+    __device__ __forceinline__ void apply(E (&af)[MT], E (&bf)[NT]) const {
+#pragma unroll
+        for (int i = 0; i < MT; ++i) af[i].y = flip(af[i].y, ma);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) bf[j].y = flip(bf[j].y, mb);
+    }
+};
+
+/// Zero the accumulator arrays of a wave tile (sub-tile by sub-tile)
+template <typename A, int MT, int NT, typename... More>
+__device__ __forceinline__ void zero_acc(A (&acc)[MT][NT], More &...more) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            acc[i][j] = A{0, 0, 0, 0};
+            ((more[i][j] = A{0, 0, 0, 0}), ...);
+        }
+}
+
+/// One k-step (4 k) of the sub-tiles (i, j) of a wave tile: acc(i, j) += af[i] * bf[j].  Complex:
+/// the 4-multiplication form in two passes over the sub-tiles, re += ar br, im += ar bi, then
+/// re += (-ai) bi, im += ai br (the order of every accumulator's MFMA chain is part of the result's
+/// bits); real: accR alone.  TRI: no MFMA for the sub-tiles below the diagonal (i > j).
+template <typename R, bool CPLX, bool TRI = false, typename E, typename A, int MT, int NT>
+__device__ __forceinline__ void mma_step(const E (&af)[MT], const E (&bf)[NT], A (&accR)[MT][NT],
+                                         A (&accI)[MT][NT]) {
+    if constexpr (CPLX) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                if (TRI && i > j) continue; // (mirrored from sub-tile (j, i))
+                accR[i][j] = Mfma<R>::mma(af[i].x, bf[j].x, accR[i][j]);
+                accI[i][j] = Mfma<R>::mma(af[i].x, bf[j].y, accI[i][j]);
+            }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                if (TRI && i > j) continue;
+                accR[i][j] = Mfma<R>::mma(-af[i].y, bf[j].y, accR[i][j]);
+                accI[i][j] = Mfma<R>::mma(af[i].y, bf[j].x, accI[i][j]);
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                if (TRI && i > j) continue;
+                accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
+            }
+    }
+}
+
+/// C(gi, gj) of batch entry bb (GROUPS = false: a launch without split label groups)
+template <typename E, bool GROUPS = true>
+__device__ __forceinline__ E *c_ptr(const GemmKArgs &p, long bb, long gi, long gj) {
+    return (E *)p.c + bb * p.sc_b + (GROUPS ? c_off(p, gi, gj) : gi * p.sc_m + gj * p.sc_n);
+}
+/// Partial of C(gi, gj) of batch entry bb in the split-K workspace: [split][batch][n][m]
+template <typename E>
+__device__ __forceinline__ E *work_ptr(const GemmKArgs &p, int split, long bb, long gi, long gj) {
+    return (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
+}
+
+/// Store the accumulator (vr, vi) of C(gi, gj): the result, or this split's partial.  The partial
+/// leaves as one element (PARTIAL_ELEM), as an element assembled first (PARTIAL_PARTS, the form
+/// gemm_wave_kernel was tuned in: the compiler shares its store instructions with the C branch),
+/// or with write-through (sc1) stores (PARTIAL_THROUGH): it reaches memory without a release
+/// fence (no L2 write-back), for a sum fused into the kernel (gemm_wave_kernel<FUSE>)
+enum PartialStore { PARTIAL_ELEM, PARTIAL_PARTS, PARTIAL_THROUGH };
+template <typename R, bool CPLX, PartialStore PS = PARTIAL_ELEM, bool GROUPS = true>
+__device__ __forceinline__ void store_acc(const GemmKArgs &p, int split, long bb, long gi, long gj,
+                                          R vr, R vi) {
+    typedef typename Elem<R, CPLX>::type E;
+    if (p.splits == 1) {
+        epilogue_store<R>((R *)c_ptr<E, GROUPS>(p, bb, gi, gj), vr, vi, p, CPLX);
+    } else if constexpr (PS == PARTIAL_ELEM) {
+        E *w = work_ptr<E>(p, split, bb, gi, gj);
+        if constexpr (CPLX) *w = E{vr, vi};
+        else *w = vr;
+    } else {
+        E *w = work_ptr<E>(p, split, bb, gi, gj);
+        E v;
+        if constexpr (CPLX) v = E{vr, vi};
+        else v = vr;
+        if constexpr (PS == PARTIAL_PARTS)
+            *w = v;
+        else if constexpr (sizeof(E) == 8)
+            __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, v),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else if constexpr (sizeof(E) == 4)
+            __hip_atomic_store((unsigned *)w, __builtin_bit_cast(unsigned, v), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        else {
+            __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, vr),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store((unsigned long long *)w + 1, __builtin_bit_cast(unsigned long long, vi),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+/// Element r of an accumulator pair to / added from an LDS slot (the sums of partial tiles over
+/// the k-groups of gemm_dma_kernel and the waves of gemm_wave_kernel)
+template <bool CPLX, typename E, typename A>
+__device__ __forceinline__ void acc_to_lds(E *slot, const A &accR, const A &accI, int r) {
+    if constexpr (CPLX) *slot = E{accR[r], accI[r]};
+    else *slot = accR[r];
+}
+template <bool CPLX, typename E, typename A>
+__device__ __forceinline__ void acc_add_lds(const E *slot, A &accR, A &accI, int r) {
+    const E v = *slot;
+    if constexpr (CPLX) {
+        accR[r] += v.x;
+        accI[r] += v.y;
+    } else {
+        accR[r] += v;
+    }
+}
+
+/// Clock probe of workgroup 0 (p.probe; tools, and the library's clock meter): the shader clock
+/// and 100 MHz reference spans from probe_begin() to probe_end() of its thread 0
+/// EVERY: every workgroup stamps when the tool asks for it (p.probe_all > 0), else workgroup 0
+template <bool EVERY = false>
+__device__ __forceinline__ void probe_begin(const GemmKArgs &p, unsigned long long &clk0,
+                                            unsigned long long &rt0) {
+    if (p.probe && (blockIdx.x == 0 || (EVERY && p.probe_all > 0))) {
+        clk0 = __builtin_amdgcn_s_memtime();
+        rt0 = __builtin_amdgcn_s_memrealtime();
+    }
+}
+__device__ __forceinline__ void probe_end(const GemmKArgs &p, unsigned long long clk0,
+                                          unsigned long long rt0) {
+    if (p.probe && blockIdx.x == 0 && threadIdx.x == 0) {
+        const unsigned long long clk1 = __builtin_amdgcn_s_memtime();
+        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
+        if (p.probe_all < 0) {
+            // the library's clock meter (tune "gemm.clock"): summed over launches with vector
+            // atomics -- shader clock cycles, 100 MHz reference ticks, launches
+            atomicAdd(&p.probe[0], clk1 - clk0);
+            atomicAdd(&p.probe[1], rt1 - rt0);
+            atomicAdd(&p.probe[2], 1ull);
+        } else {
+            p.probe[0] = clk1 - clk0; // shader clock cycles
+            p.probe[1] = rt1 - rt0;   // 100 MHz reference ticks
+        }
+    }
+}
+
 template <typename R, bool CPLX, bool AK, bool BK, int BM, int BN, int BKK, int WM, int WN>
 __global__ void __launch_bounds__(WM *WN * 64) gemm_kernel(const GemmKArgs p) {
     typedef typename Elem<R, CPLX>::type E;
@@ -171,33 +406,14 @@ __global__ void __launch_bounds__(WM *WN * 64) gemm_kernel(const GemmKArgs p) {
     __shared__ E As[BM * LDK];
     __shared__ E Bs[BN * LDK];
 
-    // XCD-aware remap: consecutive logical workgroups share an XCD (bijective form)
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-
-    const int ti = wg % p.tm;
-    int rest = wg / p.tm;
-    const int tj = rest % p.tn;
-    rest /= p.tn;
-    const int split = rest % p.splits;
-    const long bb = rest / p.splits;
-
-    const long m0 = (long)ti * BM, n0 = (long)tj * BN;
-    const long k_begin = (long)split * p.kchunk;
-    const long k_end = min(p.k, k_begin + p.kchunk);
-
-    const E *__restrict__ A = (const E *)p.a + bb * p.sa_b;
-    const E *__restrict__ B = (const E *)p.b + bb * p.sb_b;
+    const Tile t = tile_of(p, xcd_workgroup(), BM, BN);
+    const long bb = t.bb, m0 = t.m0, n0 = t.n0, k_begin = t.k_begin, k_end = t.k_end;
     const int tid = threadIdx.x;
     const bool conja = p.conja != 0, conjb = p.conjb != 0;
 
     E ra[EA], rb[EB];
-    // Wave-uniform buffer descriptors of this batch entry (T8/T20 of the CDNA guide)
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc((void *)A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)B, (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = operand_rsrc<E>(p.a, bb, p.sa_b, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = operand_rsrc<E>(p.b, bb, p.sb_b, p.b_bytes);
     constexpr unsigned OOB = 0x80000000u; // past any descriptor range: loads return 0
     auto load_stage = [&](long k0) {
 #pragma unroll
@@ -251,6 +467,7 @@ __global__ void __launch_bounds__(WM *WN * 64) gemm_kernel(const GemmKArgs p) {
     const int kq = lane >> 4;
 
     acc_t accR[MT][NT], accI[MT][NT];
+    // (spelled out: through zero_acc this kernel's register allocation changes)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -273,28 +490,7 @@ __global__ void __launch_bounds__(WM *WN * 64) gemm_kernel(const GemmKArgs p) {
             for (int i = 0; i < MT; ++i) af[i] = As[(frow + 16 * i) * LDK + kk + kq];
 #pragma unroll
             for (int j = 0; j < NT; ++j) bf[j] = Bs[(fcol + 16 * j) * LDK + kk + kq];
-            if constexpr (CPLX) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(af[i].x, bf[j].x, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].x, bf[j].y, accI[i][j]);
-                    }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(-af[i].y, bf[j].y, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].y, bf[j].x, accI[i][j]);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
-            }
+            mma_step<R, CPLX>(af, bf, accR, accI);
         }
     }
 
@@ -309,24 +505,13 @@ __global__ void __launch_bounds__(WM *WN * 64) gemm_kernel(const GemmKArgs p) {
                 const long gi = m0 + wm * WTM + 16 * i + Mfma<R>::row(lane, r);
                 const long gj = n0 + wn * WTN + 16 * j + ccol;
                 if (gi >= p.m || gj >= p.n) continue;
-                const R vr = accR[i][j][r];
-                const R vi = CPLX ? accI[i][j][r] : R(0);
-                if (p.splits == 1) {
-                    R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-                    epilogue_store<R>(cptr, vr, vi, p, CPLX);
-                } else {
-                    E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-                    if constexpr (CPLX)
-                        *w = E{vr, vi};
-                    else
-                        *w = vr;
-                }
+                store_acc<R, CPLX>(p, t.split, bb, gi, gj, accR[i][j][r], CPLX ? accI[i][j][r] : R(0));
             }
     if (p.probe && p.probe_all) {
         __syncthreads();
         if (tid == 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            p.probe[4 + 3 * bid] = __builtin_amdgcn_s_memrealtime();
+            p.probe[4 + 3 * (int)blockIdx.x] = __builtin_amdgcn_s_memrealtime();
         }
     }
 }
@@ -518,47 +703,17 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
     constexpr int LDS_E = KG > 1 && BM * BN > 2 * SLAB ? BM * BN : 2 * SLAB;
     __shared__ __attribute__((aligned(16))) E lds[LDS_E]; // the only LDS object
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    const int bid = blockIdx.x;
     static_assert(!HERM || (BM == BN && !M3 && !SH), "Hermitian output: square tiles, 4M form");
-    int ti, tj, rest;
-    if constexpr (HERM) {
-        // tile t of the upper triangle, column by column: t = tj (tj + 1) / 2 + ti, ti <= tj
-        const long ntri = (long)p.tm * (p.tm + 1) / 2;
-        const long t = wg % ntri;
-        rest = (int)(wg / ntri);
-        long c = (long)((__fsqrt_rn(8.f * (float)t + 1.f) - 1.f) * 0.5f);
-        while (c * (c + 1) / 2 > t) --c; // (the float root is off by a few at most)
-        while ((c + 1) * (c + 2) / 2 <= t) ++c;
-        tj = (int)c;
-        ti = (int)(t - c * (c + 1) / 2);
-    } else {
-        ti = wg % p.tm;
-        rest = wg / p.tm;
-        tj = rest % p.tn;
-        rest /= p.tn;
-    }
-    const int split = rest % p.splits;
-    const long bb = rest / p.splits;
-    const long m0 = (long)ti * BM, n0 = (long)tj * BN;
-    const long k_begin = (long)split * p.kchunk;
-    const long k_end = min(p.k, k_begin + p.kchunk);
-
-    const E *A = (const E *)p.a + bb * p.sa_b;
-    const E *B = (const E *)p.b + bb * p.sb_b;
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc((void *)A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)B, (short)0, (int)p.b_bytes, 0x00020000);
+    const Tile t = HERM ? upper_tile_of(p, xcd_workgroup(), BM) : tile_of(p, xcd_workgroup(), BM, BN);
+    const long bb = t.bb, m0 = t.m0, n0 = t.n0, k_begin = t.k_begin, k_end = t.k_end;
+    const __amdgpu_buffer_rsrc_t rsA = operand_rsrc<E>(p.a, bb, p.sa_b, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = operand_rsrc<E>(p.b, bb, p.sb_b, p.b_bytes);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned long long clk0 = 0, rt0 = 0;
-    if (p.probe && (bid == 0 || p.probe_all > 0)) {
-        clk0 = __builtin_amdgcn_s_memtime();
-        rt0 = __builtin_amdgcn_s_memrealtime();
-    }
+    probe_begin<true>(p, clk0, rt0);
     OpA da;
     OpB db;
     LdA la;
@@ -576,14 +731,11 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
     const int kg = KG > 1 ? wave / (WM * WN) : 0, w2 = KG > 1 ? wave % (WM * WN) : wave;
     const int wm = w2 / WN, wn = w2 % WN;
     const int frow = wm * WTM + (lane & 15), fcol = wn * WTN + (lane & 15), kq = lane >> 4;
-    // conjugation: the imaginary parts' sign bit flipped with an integer xor (no FP64 multiply)
-    typedef typename std::conditional<sizeof(R) == 8, unsigned long long, unsigned>::type U;
-    const U sign = (U)1 << (sizeof(R) * 8 - 1);
-    const U ma = p.conja ? sign : 0, mb = p.conjb ? sign : 0;
-    auto flip = [](R v, U m) { return __builtin_bit_cast(R, __builtin_bit_cast(U, v) ^ m); };
+    const ConjMask<R> cj(p);
 
     constexpr bool G3 = CPLX && M3;
     acc_t accR[MT][NT], accI[MT][NT], acc3[G3 ? MT : 1][G3 ? NT : 1];
+    // (spelled out, as in gemm_kernel)
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -622,31 +774,8 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
             for (int j = 0; j < NT; ++j) bf[j] = Bs_[OpB::slot(fcol + 16 * j, kk + kq)];
         };
         auto mma = [&](E (&af)[MT], E (&bf)[NT]) {
-            if constexpr (CPLX) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) af[i].y = flip(af[i].y, ma);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) bf[j].y = flip(bf[j].y, mb);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(af[i].x, bf[j].x, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].x, bf[j].y, accI[i][j]);
-                    }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(-af[i].y, bf[j].y, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].y, bf[j].x, accI[i][j]);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
-            }
+            if constexpr (CPLX) cj.apply(af, bf);
+            mma_step<R, CPLX>(af, bf, accR, accI);
         };
         auto issue_slab = [&](long sl, const char *dst) {
             if (!loader || sl >= nslab) return;
@@ -738,25 +867,8 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
             for (int kk = 0; kk < BKK; kk += 4) {
                 const int c = (kk / 4) & 1;
                 if (kk + 4 < BKK) frag(kk + 4, af[c ^ 1], bf[c ^ 1]);
-                E *a = af[c], *b = bf[c];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) a[i].y = flip(a[i].y, ma);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) b[j].y = flip(b[j].y, mb);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(a[i].x, b[j].x, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(a[i].x, b[j].y, accI[i][j]);
-                    }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) {
-                        accR[i][j] = Mfma<R>::mma(-a[i].y, b[j].y, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(a[i].y, b[j].x, accI[i][j]);
-                    }
+                cj.apply(af[c], bf[c]);
+                mma_step<R, true>(af[c], bf[c], accR, accI);
             }
             continue;
         }
@@ -773,12 +885,12 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
                 R as[MT], bs[NT];
 #pragma unroll
                 for (int i = 0; i < MT; ++i) {
-                    af[i].y = flip(af[i].y, ma);
+                    af[i].y = cj.flip(af[i].y, cj.ma);
                     as[i] = af[i].x + af[i].y;
                 }
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    bf[j].y = flip(bf[j].y, mb);
+                    bf[j].y = cj.flip(bf[j].y, cj.mb);
                     bs[j] = bf[j].x + bf[j].y;
                 }
 #pragma unroll
@@ -790,10 +902,8 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
                         acc3[i][j] = Mfma<R>::mma(as[i], bs[j], acc3[i][j]);
                     }
             } else if constexpr (CPLX) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) af[i].y = flip(af[i].y, ma);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) bf[j].y = flip(bf[j].y, mb);
+                // (mma_step spelled out: through the helper the KG > 1 forms compile differently)
+                cj.apply(af, bf);
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -831,12 +941,9 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            E v;
-                            if constexpr (CPLX) v = E{accR[i][j][r], accI[i][j][r]};
-                            else v = accR[i][j][r];
-                            red[(((w2 * MT + i) * NT + j) * 4 + r) * 64 + lane] = v;
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            acc_to_lds<CPLX>(&red[(((w2 * MT + i) * NT + j) * 4 + r) * 64 + lane],
+                                             accR[i][j], accI[i][j], r);
             }
             __syncthreads();
             if (kg == 0) {
@@ -845,51 +952,20 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
 #pragma unroll
                     for (int j = 0; j < NT; ++j)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const E v = red[(((w2 * MT + i) * NT + j) * 4 + r) * 64 + lane];
-                            if constexpr (CPLX) {
-                                accR[i][j][r] += v.x;
-                                accI[i][j][r] += v.y;
-                            } else {
-                                accR[i][j][r] += v;
-                            }
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            acc_add_lds<CPLX>(&red[(((w2 * MT + i) * NT + j) * 4 + r) * 64 + lane],
+                                              accR[i][j], accI[i][j], r);
             }
         }
         if (kg != 0) return;
     }
-    if (p.probe && bid == 0 && tid == 0) {
-        const unsigned long long clk1 = __builtin_amdgcn_s_memtime();
-        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-        if (p.probe_all < 0) {
-            // the library's clock meter (tune "gemm.clock"): summed over launches with vector
-            // atomics -- shader clock cycles, 100 MHz reference ticks, launches
-            atomicAdd(&p.probe[0], clk1 - clk0);
-            atomicAdd(&p.probe[1], rt1 - rt0);
-            atomicAdd(&p.probe[2], 1ull);
-        } else {
-            p.probe[0] = clk1 - clk0; // shader clock cycles
-            p.probe[1] = rt1 - rt0;   // 100 MHz reference ticks
-        }
-    }
+    probe_end(p, clk0, rt0);
     if (p.probe && p.probe_all > 0 && tid == 0) {
         p.probe[2 + 3 * bid] = rt0;
         p.probe[3 + 3 * bid] = __builtin_amdgcn_s_memrealtime();
     }
     const int ccol = lane & 15;
-    // the accumulator (vr, vi) of C(gi, gj): the result, or this split's partial
-    auto put = [&](long gi, long gj, R vr, R vi) {
-        if (p.splits == 1) {
-            R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-            epilogue_store<R>(cptr, vr, vi, p, CPLX);
-        } else {
-            E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-            if constexpr (CPLX)
-                *w = E{vr, vi};
-            else
-                *w = vr;
-        }
-    };
+    auto put = [&](long gi, long gj, R vr, R vi) { store_acc<R, CPLX>(p, t.split, bb, gi, gj, vr, vi); };
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -918,9 +994,9 @@ __global__ void __launch_bounds__(WM *WN *KG * 64) gemm_dma_kernel(const GemmKAr
 // Lean form of gemm_dma_kernel<double, true, true, true, 128, 128, 16, 4, 4, ..., LW = 8, SP = 1>
 // (complex<double>, K-major operands, 8 loader waves) for launches that need none of its
 // generality (lean_eligible: whole 128 x 128 tiles, whole 16-deep slabs, no split groups, no shared
-// slab image, default DMA policy).  The tile numbering, the slab image, the k order and partition,
-// the MFMA chain of every accumulator and the epilogue are gemm_dma_kernel's, so every output bit
-// is; what is gone is the per-piece bookkeeping of the main loop:
+// slab image, default DMA policy).  The tile numbering, the descriptors and the stores are the shared
+// helpers; the slab image, the k order and partition and the MFMA chain of every accumulator are
+// gemm_dma_kernel's, so every output bit is; what is gone is the per-piece bookkeeping of the main loop:
 //  * every DMA piece is in range: a loader lane's source offsets are computed once (one VGPR per
 //    piece), the slab's k offset is the instruction's scalar offset (one s_add per slab and
 //    operand), the LDS destination is m0 = a scalar base that flips with the buffer + a literal;
@@ -959,33 +1035,15 @@ __global__ void __launch_bounds__(1024) gemm_lean_kernel(const GemmKArgs p) {
     typedef DmaOperand<true, BM, BKK, 1024, ES> Op; // (the slab image: slot())
     __shared__ __attribute__((aligned(16))) E lds[2 * SLAB];
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
-    const int ti = wg % p.tm;
-    int rest = wg / p.tm;
-    const int tj = rest % p.tn;
-    rest /= p.tn;
-    const int split = rest % p.splits;
-    const long bb = rest / p.splits;
-    const long m0 = (long)ti * BM, n0 = (long)tj * BN;
-    const long k_begin = (long)split * p.kchunk;
-    const long k_end = min(p.k, k_begin + p.kchunk);
-
-    const E *A = (const E *)p.a + bb * p.sa_b;
-    const E *B = (const E *)p.b + bb * p.sb_b;
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc((void *)A, (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB =
-        __builtin_amdgcn_make_buffer_rsrc((void *)B, (short)0, (int)p.b_bytes, 0x00020000);
+    const Tile t = tile_of(p, xcd_workgroup(), BM, BN);
+    const long bb = t.bb, m0 = t.m0, n0 = t.n0, k_begin = t.k_begin, k_end = t.k_end;
+    const __amdgpu_buffer_rsrc_t rsA = operand_rsrc<E>(p.a, bb, p.sa_b, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = operand_rsrc<E>(p.b, bb, p.sb_b, p.b_bytes);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     unsigned long long clk0 = 0, rt0 = 0;
-    if (p.probe && bid == 0) {
-        clk0 = __builtin_amdgcn_s_memtime();
-        rt0 = __builtin_amdgcn_s_memrealtime();
-    }
+    probe_begin(p, clk0, rt0);
     // loader lanes (DmaRowsK's map): granule slot tid + 512 i is row tid / 16 + 32 i, swizzled
     // column (tid % 16) ^ (row & 15)
     const bool loader = wave < LW;
@@ -1024,13 +1082,7 @@ __global__ void __launch_bounds__(1024) gemm_lean_kernel(const GemmKArgs p) {
     }
 
     acc_t accR[MT][NT], accI[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            accR[i][j] = acc_t{0, 0, 0, 0};
-            accI[i][j] = acc_t{0, 0, 0, 0};
-        }
+    zero_acc(accR, accI);
 
     const int nslab = (int)((k_end - k_begin) / BKK); // (whole slabs)
     if (nslab > 0 && loader) issue(lbase);
@@ -1069,25 +1121,14 @@ __global__ void __launch_bounds__(1024) gemm_lean_kernel(const GemmKArgs p) {
         }
     }
 
-    if (p.probe && bid == 0 && tid == 0) {
-        const unsigned long long clk1 = __builtin_amdgcn_s_memtime();
-        const unsigned long long rt1 = __builtin_amdgcn_s_memrealtime();
-        if (p.probe_all < 0) { // the library's clock meter, as in gemm_dma_kernel
-            atomicAdd(&p.probe[0], clk1 - clk0);
-            atomicAdd(&p.probe[1], rt1 - rt0);
-            atomicAdd(&p.probe[2], 1ull);
-        } else {
-            p.probe[0] = clk1 - clk0;
-            p.probe[1] = rt1 - rt0;
-        }
-    }
+    probe_end(p, clk0, rt0);
     const int ccol = lane & 15;
     if (p.splits > 1) {
         // split-K partials through LDS (free by now), half a tile (64 columns of 128 rows, 128 KB)
         // at a time: a wave's store is 1 KB of one workspace column instead of 64-byte pieces of 16
         // columns (the 16-B row slot xor-ed with the column: conflict-free 8-lane write and
         // 16-lane read groups); the workspace layout and every bit are the generic kernel's
-        E *const w0 = (E *)p.work + (((long)split * p.batch + bb) * p.n + n0) * p.m + m0;
+        E *const w0 = work_ptr<E>(p, t.split, bb, m0, n0);
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             __syncthreads(); // the slab buffers / the previous half are read
@@ -1120,8 +1161,7 @@ __global__ void __launch_bounds__(1024) gemm_lean_kernel(const GemmKArgs p) {
             for (int r = 0; r < 4; ++r) {
                 const long gi = m0 + wm * WTM + 16 * i + Mfma<R>::row(lane, r);
                 const long gj = n0 + wn * WTN + 16 * j + ccol;
-                R *cptr = (R *)((E *)p.c + bb * p.sc_b + gi * p.sc_m + gj * p.sc_n);
-                epilogue_store<R>(cptr, accR[i][j][r], accI[i][j][r], p, true);
+                epilogue_store<R>((R *)c_ptr<E, false>(p, bb, gi, gj), accR[i][j][r], accI[i][j][r], p, true);
             }
 }
 
@@ -1163,16 +1203,13 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
     constexpr int LDS_E = KG * RING * SLAB > RED_E ? KG * RING * SLAB : RED_E;
     __shared__ __attribute__((aligned(16))) E lds[LDS_E];
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-    const int wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
+    // (one tile per batch entry: the workgroup number is split + splits * batch entry)
+    const int wg = xcd_workgroup();
     const int split = wg % p.splits;
     const long bb = wg / p.splits;
-    const long k_begin = (long)split * p.kchunk;
-    const long k_end = min(p.k, k_begin + p.kchunk);
-    const E *A = (const E *)p.a + bb * p.sa_b;
-    const __amdgpu_buffer_rsrc_t rsA =
-        __builtin_amdgcn_make_buffer_rsrc((void *)A, (short)0, (int)p.a_bytes, 0x00020000);
+    const KRange kr = split_k_range(p, split);
+    const long k_begin = kr.begin, k_end = kr.end;
+    const __amdgpu_buffer_rsrc_t rsA = operand_rsrc<E>(p.a, bb, p.sa_b, p.a_bytes);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool spl = p.split != 0;
@@ -1187,18 +1224,9 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
         da.issue(rsA, mine + (size_t)((sl - s0) % RING) * SLAB * ES, 0, k_begin + sl * BKK, k_end,
                  p.sa_k, spl, p.k_lo, p.sa_k_hi);
     };
-    typedef typename std::conditional<sizeof(R) == 8, unsigned long long, unsigned>::type U;
-    const U sign = (U)1 << (sizeof(R) * 8 - 1);
-    const U ma = p.conja ? sign : 0, mb = p.conjb ? sign : 0;
-    auto flip = [](R v, U m) { return __builtin_bit_cast(R, __builtin_bit_cast(U, v) ^ m); };
+    const ConjMask<R> cj(p);
     acc_t accR[MT][MT], accI[MT][MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < MT; ++j) {
-            accR[i][j] = acc_t{0, 0, 0, 0};
-            accI[i][j] = acc_t{0, 0, 0, 0};
-        }
+    zero_acc(accR, accI);
     const int frow = lane & 15, kq = lane >> 4;
 #pragma unroll
     for (int r = 0; r < RING - 1; ++r)
@@ -1228,36 +1256,8 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
             for (int i = 0; i < MT; ++i) af[i] = As[Op::slot(frow + 16 * i, kk + kq)];
 #pragma unroll
             for (int j = 0; j < MT; ++j) bf[j] = af[j]; // the same image: B's fragment = A's
-            if constexpr (CPLX) {
-#pragma unroll
-                for (int i = 0; i < MT; ++i) af[i].y = flip(af[i].y, ma);
-#pragma unroll
-                for (int j = 0; j < MT; ++j) bf[j].y = flip(bf[j].y, mb);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < MT; ++j) {
-                        if (HERM && i > j) continue; // (mirrored from sub-tile (j, i))
-                        accR[i][j] = Mfma<R>::mma(af[i].x, bf[j].x, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].x, bf[j].y, accI[i][j]);
-                    }
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < MT; ++j) {
-                        if (HERM && i > j) continue;
-                        accR[i][j] = Mfma<R>::mma(-af[i].y, bf[j].y, accR[i][j]);
-                        accI[i][j] = Mfma<R>::mma(af[i].y, bf[j].x, accI[i][j]);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < MT; ++j) {
-                        if (HERM && i > j) continue;
-                        accR[i][j] = Mfma<R>::mma(af[i], bf[j], accR[i][j]);
-                    }
-            }
+            if constexpr (CPLX) cj.apply(af, bf);
+            mma_step<R, CPLX, HERM>(af, bf, accR, accI);
         }
     }
     // the waves' partial tiles summed into wave 0 by a fixed binary tree (wave w + step into wave
@@ -1274,10 +1274,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (HERM && i > j) continue; // (live sub-tiles only)
-                        E v;
-                        if constexpr (CPLX) v = E{accR[i][j][r], accI[i][j][r]};
-                        else v = accR[i][j][r];
-                        red[((i * MT + j) * 4 + r) * 64 + lane] = v;
+                        acc_to_lds<CPLX>(&red[((i * MT + j) * 4 + r) * 64 + lane], accR[i][j], accI[i][j], r);
                     }
         }
         __syncthreads();
@@ -1289,49 +1286,16 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (HERM && i > j) continue;
-                        const E v = red[((i * MT + j) * 4 + r) * 64 + lane];
-                        if constexpr (CPLX) {
-                            accR[i][j][r] += v.x;
-                            accI[i][j][r] += v.y;
-                        } else {
-                            accR[i][j][r] += v;
-                        }
+                        acc_add_lds<CPLX>(&red[((i * MT + j) * 4 + r) * 64 + lane], accR[i][j], accI[i][j], r);
                     }
         }
     }
     const bool fuse = FUSE && p.splits > 1;
     if (wave != 0 && !fuse) return;
     if (wave == 0) {
-        // the accumulator (vr, vi) of C(gi, gj): the result, or this split's partial
+        // (FUSE: the partials leave with write-through stores)
         auto put = [&](long gi, long gj, R vr, R vi) {
-            if (p.splits == 1) {
-                R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-                epilogue_store<R>(cptr, vr, vi, p, CPLX);
-            } else {
-                E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-                E v;
-                if constexpr (CPLX) v = E{vr, vi};
-                else v = vr;
-                if constexpr (FUSE) {
-                    // write-through (sc1) stores: the partial reaches memory without a
-                    // release fence (no L2 write-back)
-                    if constexpr (sizeof(E) == 8)
-                        __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, v),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else if constexpr (sizeof(E) == 4)
-                        __hip_atomic_store((unsigned *)w, __builtin_bit_cast(unsigned, v),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else {
-                        const R re = vr, im = vi;
-                        __hip_atomic_store((unsigned long long *)w, __builtin_bit_cast(unsigned long long, re),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store((unsigned long long *)w + 1, __builtin_bit_cast(unsigned long long, im),
-                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                } else {
-                    *w = v;
-                }
-            }
+            store_acc<R, CPLX, FUSE ? PARTIAL_THROUGH : PARTIAL_PARTS>(p, split, bb, gi, gj, vr, vi);
         };
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -1390,8 +1354,7 @@ __global__ void __launch_bounds__(KG * 64) gemm_wave_kernel(const GemmKArgs p, u
                     sr += v;
                 }
             }
-            R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
-            epilogue_store<R>(cptr, sr, si, p, CPLX);
+            epilogue_store<R>((R *)c_ptr<E>(p, bb, gi, gj), sr, si, p, CPLX);
         }
         if (tid == 0) __hip_atomic_store(counters + bb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1424,10 +1387,11 @@ template <typename E> __device__ __forceinline__ E xor_sum(E v, int m) {
         return v + __shfl_xor(v, m);
 }
 template <typename R, bool CPLX> __device__ __forceinline__ void store_out(const GemmKArgs &p, long bb, long gi, long gj, typename Elem<R, CPLX>::type v) {
+    R *cptr = (R *)c_ptr<typename Elem<R, CPLX>::type, false>(p, bb, gi, gj);
     if constexpr (CPLX)
-        epilogue_store<R>((R *)((typename Elem<R, CPLX>::type *)p.c + bb * p.sc_b + gi * p.sc_m + gj * p.sc_n), v.x, v.y, p, true);
+        epilogue_store<R>(cptr, v.x, v.y, p, true);
     else
-        epilogue_store<R>((R *)p.c + bb * p.sc_b + gi * p.sc_m + gj * p.sc_n, v, R(0), p, false);
+        epilogue_store<R>(cptr, v, R(0), p, false);
 }
 
 template <typename R, bool CPLX, int MM, int NN>
@@ -1435,7 +1399,8 @@ __global__ void __launch_bounds__(256) gemm_dot_kernel(const GemmKArgs p) {
     typedef typename Elem<R, CPLX>::type E;
     const int split = (int)(blockIdx.x % (unsigned)p.splits);
     const long bb = blockIdx.x / (unsigned)p.splits;
-    const long k0 = (long)split * p.kchunk, k1 = min(p.k, k0 + p.kchunk);
+    const KRange kr = split_k_range(p, split);
+    const long k0 = kr.begin, k1 = kr.end;
     const E *A = (const E *)p.a + bb * p.sa_b, *B = (const E *)p.b + bb * p.sb_b;
     const int m = (int)p.m, n = (int)p.n;
     E acc[MM][NN];
@@ -1555,10 +1520,8 @@ __global__ void __launch_bounds__(256) gemm_frag_kernel(const GemmKArgs p) {
     const long bb = rest / p.tn;
     const long m0 = ti * 16, n0 = tj * 16 * NT;
     const long k_begin = (long)split * p.kchunk, k_end = min(p.k, k_begin + p.kchunk);
-    const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const E *)p.a + bb * p.sa_b), (short)0, (int)p.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const E *)p.b + bb * p.sb_b), (short)0, (int)p.b_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsA = operand_rsrc<E>(p.a, bb, p.sa_b, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rsB = operand_rsrc<E>(p.b, bb, p.sb_b, p.b_bytes);
     const int r = lane & 15, q = lane >> 4;
     const bool okA = m0 + r < p.m;
     const long baseA = (m0 + r) * p.sa_m;
@@ -1569,10 +1532,7 @@ __global__ void __launch_bounds__(256) gemm_frag_kernel(const GemmKArgs p) {
         okB[j] = n0 + 16 * j + r < p.n;
         baseB[j] = (n0 + 16 * j + r) * p.sb_n;
     }
-    typedef typename std::conditional<sizeof(R) == 8, unsigned long long, unsigned>::type U;
-    const U sign = (U)1 << (sizeof(R) * 8 - 1);
-    const U ma = p.conja ? sign : 0, mb = p.conjb ? sign : 0;
-    auto flip = [](R v, U m) { return __builtin_bit_cast(R, __builtin_bit_cast(U, v) ^ m); };
+    const ConjMask<R> cj(p);
     static_assert(!KP || (ES == 8 && UK % 2 == 0), "k pairs: 8-byte elements, even UK");
     auto load = [&](long k0, E (&a)[UK], E (&b)[NT][UK]) {
         if constexpr (KP) {
@@ -1625,10 +1585,10 @@ __global__ void __launch_bounds__(256) gemm_frag_kernel(const GemmKArgs p) {
 #pragma unroll
         for (int u = 0; u < UK; ++u) {
             if constexpr (CPLX) {
-                const R ar = a[u].x, ai = flip(a[u].y, ma);
+                const R ar = a[u].x, ai = cj.flip(a[u].y, cj.ma);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    const R br = b[j][u].x, bi = flip(b[j][u].y, mb);
+                    const R br = b[j][u].x, bi = cj.flip(b[j][u].y, cj.mb);
                     accR[j] = Mfma<R>::mma(ar, br, accR[j]);
                     accI[j] = Mfma<R>::mma(ar, bi, accI[j]);
                     accR[j] = Mfma<R>::mma(-ai, bi, accR[j]);
@@ -1652,16 +1612,8 @@ __global__ void __launch_bounds__(256) gemm_frag_kernel(const GemmKArgs p) {
         for (int i = 0; i < 4; ++i) {
             const long gi = m0 + Mfma<R>::row(lane, i), gj = n0 + 16 * j + r;
             if (gi >= p.m || gj >= p.n) continue;
-            const R vr = accR[j][i], vi = CPLX ? accI[j][i] : R(0);
-            if (p.splits == 1) {
-                epilogue_store<R>((R *)((E *)p.c + bb * p.sc_b + gi * p.sc_m + gj * p.sc_n), vr, vi, p, CPLX);
-            } else {
-                E *w = (E *)p.work + (((long)split * p.batch + bb) * p.n + gj) * p.m + gi;
-                if constexpr (CPLX)
-                    *w = E{vr, vi};
-                else
-                    *w = vr;
-            }
+            // (GROUPS = false: launch_frag takes no split label groups)
+            store_acc<R, CPLX, PARTIAL_ELEM, false>(p, split, bb, gi, gj, accR[j][i], CPLX ? accI[j][i] : R(0));
         }
     }
 }
@@ -1703,12 +1655,19 @@ __global__ void __launch_bounds__(256) scale_c_kernel(const GemmKArgs p) {
         const long gi = idx % p.m;
         const long gj = (idx / p.m) % p.n;
         const long bb = idx / (p.m * p.n);
-        R *cptr = (R *)((E *)p.c + bb * p.sc_b + c_off(p, gi, gj));
+        R *cptr = (R *)c_ptr<E>(p, bb, gi, gj);
         GemmKArgs q = p;
         q.alpha_re = 0;
         q.alpha_im = 0;
         epilogue_store<R>(cptr, R(0), R(0), q, CPLX);
     }
+}
+
+/// Largest element offset of an index group of extent n: split groups (inner extent lo, strides
+/// (st_hi, st)), or one run of stride st (lo <= 0 or lo >= n)
+long group_extent(long n, long lo, long st, long st_hi) {
+    return lo > 0 && lo < n ? (n / lo - 1) * std::labs(st_hi) + (lo - 1) * std::labs(st)
+                            : (n - 1) * std::labs(st);
 }
 
 /// Grid shape, split-K factor, descriptor ranges and the split-K workspace of one launch
@@ -1727,18 +1686,10 @@ long prepare_launch(GemmKArgs &p, int BM, int BN, int BKK, long splits, long tar
             splits = std::min(splits, max_splits);
         }
     }
-    // largest element offset of a split (or plain) group index
-    auto ext = [](long n, long lo, long st, long st_hi) {
-        return (n / lo - 1) * std::labs(st_hi) + (lo - 1) * std::labs(st);
-    };
-    const long ea = p.split ? (ext(p.m, p.m_lo, p.sa_m, p.sa_m_hi) +
-                               ext(p.k, p.k_lo, p.sa_k, p.sa_k_hi) + 1) * (long)sizeof(E)
-                            : ((p.m - 1) * std::labs(p.sa_m) + (p.k - 1) * std::labs(p.sa_k) + 1) *
-                                  (long)sizeof(E);
-    const long eb = p.split ? (ext(p.k, p.k_lo, p.sb_k, p.sb_k_hi) +
-                               ext(p.n, p.n_lo, p.sb_n, p.sb_n_hi) + 1) * (long)sizeof(E)
-                            : ((p.k - 1) * std::labs(p.sb_k) + (p.n - 1) * std::labs(p.sb_n) + 1) *
-                                  (long)sizeof(E);
+    const long ea = (group_extent(p.m, p.m_lo, p.sa_m, p.sa_m_hi) +
+                     group_extent(p.k, p.k_lo, p.sa_k, p.sa_k_hi) + 1) * (long)sizeof(E);
+    const long eb = (group_extent(p.k, p.k_lo, p.sb_k, p.sb_k_hi) +
+                     group_extent(p.n, p.n_lo, p.sb_n, p.sb_n_hi) + 1) * (long)sizeof(E);
     if (ea >= 0x7fffffffL || eb >= 0x7fffffffL || p.sa_m < 0 || p.sa_k < 0 || p.sb_k < 0 ||
         p.sb_n < 0 || p.sa_m_hi < 0 || p.sa_k_hi < 0 || p.sb_k_hi < 0 || p.sb_n_hi < 0)
         throw Error("gemm: operand batch entries of 2 GiB or more are not supported yet");
@@ -1773,9 +1724,8 @@ template <typename E> int herm_mode(const GemmKArgs &p, bool cplx) {
     if (!g_gemm_tune.herm || !same_operands(p)) return 0;
     if (p.sc_m < 0 || p.sc_n < 0 || p.sc_b < 0 || p.sc_m_hi < 0 || p.sc_n_hi < 0 || p.sa_b < 0)
         return 0;
-    auto ext = [](long n, long lo, long st, long st_hi) { return (n / lo - 1) * st_hi + (lo - 1) * st; };
-    const long ec = p.split ? ext(p.m, p.m_lo, p.sc_m, p.sc_m_hi) + ext(p.n, p.n_lo, p.sc_n, p.sc_n_hi)
-                            : (p.m - 1) * p.sc_m + (p.n - 1) * p.sc_n;
+    const long ec = group_extent(p.m, p.m_lo, p.sc_m, p.sc_m_hi) +
+                    group_extent(p.n, p.n_lo, p.sc_n, p.sc_n_hi);
     const char *c0 = (const char *)p.c, *c1 = c0 + ((p.batch - 1) * p.sc_b + ec + 1) * (long)sizeof(E);
     const char *a0 = (const char *)p.a, *a1 = a0 + (p.batch - 1) * p.sa_b * (long)sizeof(E) + p.a_bytes;
     if (c0 < a1 && a0 < c1) return 0; // C aliases A
@@ -1793,6 +1743,21 @@ void launch_reduce(const GemmKArgs &p, hipStream_t stream) {
     SBX_HIP_CHECK(hipGetLastError());
 }
 
+/// The skeleton of every launcher: `launch` issues the kernel(s) of the prepared launch p, then
+/// the split-K partials are summed unless the kernel does that itself (fused_sum).
+/// "gemm_total": one event pair around the GEMM launch and its split-K reduce (the bench's
+/// roofline timer: two event records per GEMM instead of four); it begins first and ends last
+template <typename R, bool CPLX, typename F>
+void timed_launch(const GemmKArgs &p, hipStream_t stream, F &&launch, bool fused_sum = false) {
+    KernelTimer total("gemm_total", stream);
+    {
+        KernelTimer timer("gemm", stream);
+        launch();
+        SBX_HIP_CHECK(hipGetLastError());
+    }
+    if (!fused_sum) launch_reduce<R, CPLX>(p, stream);
+}
+
 /// Launch one tile configuration of the register-staged kernel
 template <typename R, bool CPLX, bool AK, bool BK, int BM, int BN, int BKK, int WM, int WN>
 void launch_tiled_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long splits = 0,
@@ -1801,16 +1766,10 @@ void launch_tiled_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long 
     Scratch work;
     const long nwg = prepare_launch<typename Elem<R, CPLX>::type>(p, BM, BN, BKK, splits,
                                                                    target_wgs, work, device);
-    // "gemm_total": one event pair around the GEMM launch and its split-K reduce (the bench's
-    // roofline timer: two event records per GEMM instead of four)
-    KernelTimer total("gemm_total", stream);
-    {
-        KernelTimer timer("gemm", stream);
+    timed_launch<R, CPLX>(p, stream, [&] {
         hipLaunchKernelGGL((gemm_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN>),
                            dim3((unsigned)nwg), dim3(WM * WN * 64), 0, stream, p);
-        SBX_HIP_CHECK(hipGetLastError());
-    }
-    launch_reduce<R, CPLX>(p, stream);
+    });
 }
 
 /// The clock meter of the LDS-DMA kernel (tune key "gemm.clock" > 0): workgroup 0 of every
@@ -1831,6 +1790,14 @@ unsigned long long *gemm_clock_meter(int device) {
         g_clock_meter[device] = (unsigned long long *)ptr;
     }
     return g_clock_meter[device];
+}
+
+/// Point a launch's probe at the device's clock meter, when it is on
+void attach_clock_meter(GemmKArgs &p, int device) {
+    if (unsigned long long *meter = gemm_clock_meter(device)) {
+        p.probe = meter;
+        p.probe_all = -1;
+    }
 }
 
 void clock_read_impl(int device, unsigned long long out[3], bool reset) {
@@ -1874,23 +1841,16 @@ void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long sp
             g_gemm_tune.last_herm = p.tm * (p.tm - 1) / 2;
         }
     }
-    if (unsigned long long *meter = gemm_clock_meter(device)) {
-        p.probe = meter;
-        p.probe_all = -1;
-    }
-    KernelTimer total("gemm_total", stream);
-    {
-        KernelTimer timer("gemm", stream);
-        bool launched = false;
+    attach_clock_meter(p, device);
+    timed_launch<R, CPLX>(p, stream, [&] {
         if constexpr (HERM_OK) {
             if (p.herm) {
                 hipLaunchKernelGGL((gemm_dma_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN, false, PF, KG, SH, LW, SP, true>),
                                    dim3((unsigned)nwg), dim3(WM * WN * KG * 64), 0, stream, p);
-                launched = true;
+                return;
             }
         }
-        if (launched) {
-        } else if constexpr (ALLOW_M3) {
+        if constexpr (ALLOW_M3) {
             if (m3)
                 hipLaunchKernelGGL((gemm_dma_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN, CPLX>),
                                    dim3((unsigned)nwg), dim3(WM * WN * 64), 0, stream, p);
@@ -1900,9 +1860,7 @@ void launch_dma_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long sp
         } else
             hipLaunchKernelGGL((gemm_dma_kernel<R, CPLX, AK, BK, BM, BN, BKK, WM, WN, false, PF, KG, SH, LW, SP>),
                                dim3((unsigned)nwg), dim3(WM * WN * KG * 64), 0, stream, p);
-        SBX_HIP_CHECK(hipGetLastError());
-    }
-    launch_reduce<R, CPLX>(p, stream);
+    });
 }
 
 /// A complex<double> K-major launch that gemm_lean_kernel can take in place of the 128x128x16
@@ -1922,26 +1880,16 @@ void launch_lean(const GemmKArgs &p0, int device, hipStream_t stream) {
     Scratch work;
     const long nwg = prepare_launch<double2>(p, 128, 128, 16, g_gemm_tune.splits > 0 ? g_gemm_tune.splits : 0,
                                              256, work, device);
-    if (unsigned long long *meter = gemm_clock_meter(device)) {
-        p.probe = meter;
-        p.probe_all = -1;
-    }
+    attach_clock_meter(p, device);
     g_gemm_tune.last_lean = 1;
-    KernelTimer total("gemm_total", stream);
-    {
-        KernelTimer timer("gemm", stream);
-        const dim3 grid((unsigned)nwg), block(1024);
-        if (p.conja && p.conjb)
-            hipLaunchKernelGGL((gemm_lean_kernel<true, true>), grid, block, 0, stream, p);
-        else if (p.conja)
-            hipLaunchKernelGGL((gemm_lean_kernel<true, false>), grid, block, 0, stream, p);
-        else if (p.conjb)
-            hipLaunchKernelGGL((gemm_lean_kernel<false, true>), grid, block, 0, stream, p);
-        else
-            hipLaunchKernelGGL((gemm_lean_kernel<false, false>), grid, block, 0, stream, p);
-        SBX_HIP_CHECK(hipGetLastError());
-    }
-    launch_reduce<double, true>(p, stream);
+    timed_launch<double, true>(p, stream, [&] {
+        auto go = [&](auto ca, auto cb) {
+            hipLaunchKernelGGL((gemm_lean_kernel<decltype(ca)::value, decltype(cb)::value>),
+                               dim3((unsigned)nwg), dim3(1024), 0, stream, p);
+        };
+        auto by_b = [&](auto ca) { p.conjb ? go(ca, std::true_type()) : go(ca, std::false_type()); };
+        p.conja ? by_b(std::true_type()) : by_b(std::false_type());
+    });
 }
 
 /// The fused split-K sums' per-batch-entry counters of a stream: zero when allocated and left zero
@@ -1984,18 +1932,14 @@ void launch_wave_cfg(const GemmKArgs &p0, int device, hipStream_t stream, long t
     constexpr int MT = BM / 16;
     p.herm = MT > 1 ? herm_mode<typename Elem<R, CPLX>::type>(p, CPLX) : 0;
     if (p.herm) g_gemm_tune.last_herm = MT * (MT - 1) / 2;
-    KernelTimer total("gemm_total", stream);
-    {
-        KernelTimer timer("gemm", stream);
+    timed_launch<R, CPLX>(p, stream, [&] {
         if (p.herm)
             hipLaunchKernelGGL((gemm_wave_kernel<R, CPLX, AK, BM, BKK, KG, RING, FUSE, true>),
                                dim3((unsigned)nwg), dim3(KG * 64), 0, stream, p, counters);
         else
             hipLaunchKernelGGL((gemm_wave_kernel<R, CPLX, AK, BM, BKK, KG, RING, FUSE>),
                                dim3((unsigned)nwg), dim3(KG * 64), 0, stream, p, counters);
-        SBX_HIP_CHECK(hipGetLastError());
-    }
-    if (!FUSE) launch_reduce<R, CPLX>(p, stream);
+    }, FUSE);
 }
 
 /// The LDS-DMA kernel reads whole 16-B granules: every granule must lie inside the operand
@@ -2139,9 +2083,7 @@ template <typename R, bool CPLX> bool launch_skinny(const GemmKArgs &p0, int dev
         }
         const long nwg = p.batch * splits;
         if (nwg > 0x7fffffffL) return false;
-        KernelTimer total("gemm_total", s);
-        {
-            KernelTimer timer("gemm", s);
+        timed_launch<R, CPLX>(p, s, [&] {
             const long mx = std::max(p.m, p.n);
             if (mx == 1)
                 hipLaunchKernelGGL((gemm_dot_kernel<R, CPLX, 1, 1>), dim3((unsigned)nwg), dim3(256), 0, s, p);
@@ -2149,9 +2091,7 @@ template <typename R, bool CPLX> bool launch_skinny(const GemmKArgs &p0, int dev
                 hipLaunchKernelGGL((gemm_dot_kernel<R, CPLX, 2, 2>), dim3((unsigned)nwg), dim3(256), 0, s, p);
             else
                 hipLaunchKernelGGL((gemm_dot_kernel<R, CPLX, 4, 4>), dim3((unsigned)nwg), dim3(256), 0, s, p);
-            SBX_HIP_CHECK(hipGetLastError());
-        }
-        launch_reduce<R, CPLX>(p, s);
+        });
         return true;
     }
     // one long output dimension, the other <= 16, and a short k (updates): a lane per output
@@ -2171,19 +2111,19 @@ template <typename R, bool CPLX> bool launch_skinny(const GemmKArgs &p0, int dev
     }
     const long total = p.m * p.batch;
     const long blocks = std::max(1L, std::min((total + 255) / 256, 65536L));
-    KernelTimer total_t("gemm_total", s);
-    KernelTimer timer("gemm", s);
-    if (p.n == 1)
-        hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 1>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (p.n <= 2)
-        hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 2>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (p.n <= 4)
-        hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 4>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else if (p.n <= 8)
-        hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 8>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    else
-        hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
-    SBX_HIP_CHECK(hipGetLastError());
+    // (no split-K here: p.splits is 1 and the skeleton's reduce is a no-op)
+    timed_launch<R, CPLX>(p, s, [&] {
+        if (p.n == 1)
+            hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 1>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else if (p.n <= 2)
+            hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 2>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else if (p.n <= 4)
+            hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 4>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else if (p.n <= 8)
+            hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 8>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+        else
+            hipLaunchKernelGGL((gemm_rows_kernel<R, CPLX, 16>), dim3((unsigned)blocks), dim3(256), 0, s, p);
+    });
     return true;
 }
 
@@ -2248,9 +2188,7 @@ template <typename R, bool CPLX> bool launch_frag(const GemmKArgs &p0, int devic
     // products with an m-contiguous A, B alone paired: within 3 %, profiles/r06_gemm_frag_pairs_nn.txt)
     const bool kp = E8 && g_gemm_tune.frag_pair && p.k % 2 == 0 &&
                     (p.pair_a || (p.pair_b && p.n > 16));
-    KernelTimer total("gemm_total", s);
-    {
-        KernelTimer timer("gemm", s);
+    timed_launch<R, CPLX>(p, s, [&] {
         const dim3 grid((unsigned)blocks), wg(256);
         auto go = [&](auto ukc, auto kpc, auto ntc) {
             constexpr int UKv = decltype(ukc)::value, NTv = decltype(ntc)::value;
@@ -2277,9 +2215,7 @@ template <typename R, bool CPLX> bool launch_frag(const GemmKArgs &p0, int devic
             if (kp) by_uk(std::true_type());
         }
         if (!kp) by_uk(std::false_type());
-        SBX_HIP_CHECK(hipGetLastError());
-    }
-    launch_reduce<R, CPLX>(p, s);
+    });
     return true;
 }
 
@@ -2349,6 +2285,29 @@ GemmKArgs make_args(const GemmDesc &d) {
     return p;
 }
 
+/// Run a GEMM as two, its extent n (M, N or K; inner extent lo of split groups, 0 = one run) cut in
+/// half: split groups only between outer indices.  The second part's pointers p1 and p2 (the
+/// operand(s) or C that n addresses) move on by the cut in their stride pairs (s, s_hi); a K cut's
+/// second part accumulates (beta = 1)
+template <typename P1, typename P2>
+void bisect_gemm(const GemmDesc &d, int device, long GemmDesc::*n, long GemmDesc::*lo,
+                 P1 GemmDesc::*p1, long s1, long s1_hi, P2 GemmDesc::*p2, long s2, long s2_hi,
+                 bool accumulate) {
+    const bool groups = d.*lo > 0 && d.*lo < d.*n;
+    const long o = groups ? d.*n / d.*lo / 2 : d.*n / 2; // outer indices (elements) of part one
+    const long n1 = groups ? o * d.*lo : o;
+    const long es = (long)dtype_size(d.t);
+    GemmDesc a = d, b = d;
+    a.*n = n1;
+    b.*n = d.*n - n1;
+    a.*lo = b.*lo = groups ? d.*lo : 0;
+    b.*p1 = (P1)((const char *)(d.*p1) + es * o * (groups ? s1_hi : s1));
+    b.*p2 = (P2)((const char *)(d.*p2) + es * o * (groups ? s2_hi : s2));
+    if (accumulate) b.beta = Scalar{1, 0};
+    launch_gemm(a, device);
+    launch_gemm(b, device);
+}
+
 } // namespace
 
 void gemm_clock_read(int device, unsigned long long out[3], bool reset) {
@@ -2362,74 +2321,22 @@ void launch_gemm(const GemmDesc &d, int device) {
     if (d.k > 0 && (d.alpha.re != 0 || d.alpha.im != 0)) {
         const long es = (long)dtype_size(d.t);
         const long max_bytes = g_gemm_tune.max_bytes > 0 ? g_gemm_tune.max_bytes : (1L << 31) - 1;
-        auto ext = [&](long n, long lo, long st, long st_hi) {
-            return lo > 0 && lo < n ? (n / lo - 1) * std::labs(st_hi) + (lo - 1) * std::labs(st)
-                                    : (n - 1) * std::labs(st);
-        };
-        const long ea = (ext(d.m, d.m_lo, d.sa_m, d.sa_m_hi) + ext(d.k, d.k_lo, d.sa_k, d.sa_k_hi) + 1) * es;
-        const long eb = (ext(d.k, d.k_lo, d.sb_k, d.sb_k_hi) + ext(d.n, d.n_lo, d.sb_n, d.sb_n_hi) + 1) * es;
+        const long ea = (group_extent(d.m, d.m_lo, d.sa_m, d.sa_m_hi) +
+                         group_extent(d.k, d.k_lo, d.sa_k, d.sa_k_hi) + 1) * es;
+        const long eb = (group_extent(d.k, d.k_lo, d.sb_k, d.sb_k_hi) +
+                         group_extent(d.n, d.n_lo, d.sb_n, d.sb_n_hi) + 1) * es;
         if (ea > max_bytes || eb > max_bytes) {
-            // cut a group of extent n (inner extent lo, 0 = one run) in two: split groups only
-            // between outer indices; returns the first part's extent and the second's offset
-            // (in elements, per stride pair)
-            struct Cut {
-                long n1, lo1, n2, lo2, o_outer;
-                bool ok;
-            };
-            auto cut = [](long n, long lo) {
-                Cut c{};
-                const bool spl = lo > 0 && lo < n;
-                if (spl) {
-                    const long outer = n / lo, o1 = outer / 2;
-                    c = Cut{o1 * lo, lo, n - o1 * lo, lo, o1, true};
-                } else {
-                    c = Cut{n / 2, 0, n - n / 2, 0, n / 2, n > 1};
-                }
-                return c;
-            };
-            // element offset of the second part for one operand's strides
-            auto off = [](long n, long lo, long st, long st_hi, long o) {
-                return lo > 0 && lo < n ? o * st_hi : o * st;
-            };
-            const Cut ck = cut(d.k, d.k_lo);
-            if (ck.ok) {
-                GemmDesc a = d, b = d;
-                a.k = ck.n1;
-                a.k_lo = ck.lo1;
-                b.k = ck.n2;
-                b.k_lo = ck.lo2;
-                b.a = (const char *)d.a + es * off(d.k, d.k_lo, d.sa_k, d.sa_k_hi, ck.o_outer);
-                b.b = (const char *)d.b + es * off(d.k, d.k_lo, d.sb_k, d.sb_k_hi, ck.o_outer);
-                b.beta = Scalar{1, 0};
-                launch_gemm(a, device);
-                launch_gemm(b, device);
-                return;
-            }
-            const Cut cm = cut(d.m, d.m_lo), cn = cut(d.n, d.n_lo);
-            if (cm.ok && (ea > max_bytes || !cn.ok)) {
-                GemmDesc a = d, b = d;
-                a.m = cm.n1;
-                a.m_lo = cm.lo1;
-                b.m = cm.n2;
-                b.m_lo = cm.lo2;
-                b.a = (const char *)d.a + es * off(d.m, d.m_lo, d.sa_m, d.sa_m_hi, cm.o_outer);
-                b.c = (char *)d.c + es * off(d.m, d.m_lo, d.sc_m, d.sc_m_hi, cm.o_outer);
-                launch_gemm(a, device);
-                launch_gemm(b, device);
-                return;
-            }
-            if (cn.ok) {
-                GemmDesc a = d, b = d;
-                a.n = cn.n1;
-                a.n_lo = cn.lo1;
-                b.n = cn.n2;
-                b.n_lo = cn.lo2;
-                b.b = (const char *)d.b + es * off(d.n, d.n_lo, d.sb_n, d.sb_n_hi, cn.o_outer);
-                b.c = (char *)d.c + es * off(d.n, d.n_lo, d.sc_n, d.sc_n_hi, cn.o_outer);
-                launch_gemm(a, device);
-                launch_gemm(b, device);
-                return;
-            }
+            // K first, then M if A is the oversized operand or N cannot be cut, then N (an extent
+            // of one cannot be cut)
+            if (d.k > 1)
+                return bisect_gemm(d, device, &GemmDesc::k, &GemmDesc::k_lo, &GemmDesc::a, d.sa_k,
+                                   d.sa_k_hi, &GemmDesc::b, d.sb_k, d.sb_k_hi, true);
+            if (d.m > 1 && (ea > max_bytes || d.n <= 1))
+                return bisect_gemm(d, device, &GemmDesc::m, &GemmDesc::m_lo, &GemmDesc::a, d.sa_m,
+                                   d.sa_m_hi, &GemmDesc::c, d.sc_m, d.sc_m_hi, false);
+            if (d.n > 1)
+                return bisect_gemm(d, device, &GemmDesc::n, &GemmDesc::n_lo, &GemmDesc::b, d.sb_n,
+                                   d.sb_n_hi, &GemmDesc::c, d.sc_n, d.sc_n_hi, false);
             throw Error("gemm: operand batch entries of 2 GiB or more are not supported");
         }
     }
