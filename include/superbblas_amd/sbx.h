@@ -115,9 +115,15 @@ int sbx_timings_report(char *buf, int len);
    output tiles and mirror the rest; 0 = off, the default), "gemm.loaders", "gemm.dma_spread", "gemm.skinny", "copy.nt", "copy.budget", "copy.run", "copy.max_elems", "copy.pair",
    "copy.order", "copy.trans", "copy.btrans", "bsr.variant", "bsr.row_max_cols", "bsr.split_max_cols",
    "bsr.split_cw", "bsr.split_jb", "bsr.split_ilv", "bsr.kron_mfma", "bsr.kron_mfma_min_cols",
-   "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.nt", "bsr.blk_pd", "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
+   "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.nt", "bsr.blk_pd", "bsr.blk_mfma" (dense blocks of
+   "bsr.blk_min" x "bsr.blk_min" and more -- default 16, the multigrid coarse operators -- on the matrix-core
+   kernel bsr_blk_mfma_kernel: 1, the default, where it was measured faster than the generic kernel -- blocks
+   of 1024 elements and more at any rhs column count, of 576 and more from 4 columns, smaller ones from 12;
+   2 at any column count; 0 the generic kernel; 3x3, 12x12 and Kronecker operators keep their kernels),
+   "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
-   "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel", "dist.peer_copies",
+   "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
+   last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel), "dist.peer_copies",
    "copy.last_pair", "gemm.last_herm" (tiles per batch entry the last GEMM launch mirrored instead
    of computed; 0 = a full product), "gemm.last_lean" (1 when the last GEMM launch took the lean form of
    the complex<double> 128x128x16 kernel, key "gemm.lean", on by default and bit-identical to the generic

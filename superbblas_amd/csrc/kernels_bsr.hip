@@ -1400,6 +1400,248 @@ void launch_layouts(const BsrArgs &a, bool yrow, bool xrow, long blocks, hipStre
     SBX_HIP_CHECK(hipGetLastError());
 }
 
+// Dense blocks of 16 x 16 and more (the multigrid coarse operators: (2 nv) x (2 nv) blocks, 9
+// per row, 1-64 rhs columns) on the matrix cores.  One workgroup per block row and group of NT
+// tiles of 16 rhs columns; wave w owns the 16-row strip w % nstrips of the row (at most 8
+// strips, bi <= 128).  Per nonzero block:
+//  * the workgroup stages the bd x 16 NT piece of x once into LDS (any x layout; rows past bd
+//    and columns past ncols as zeros), one block ahead in two buffers, so one barrier per block.
+//    The LDS image keeps the VE = 16 / sizeof(E) consecutive k of a column together: a B
+//    fragment of VE k-steps is one 16-byte LDS read;
+//  * a wave reads its strip of the value block straight into A fragments: lane (row r, k-group
+//    kq) takes the VE consecutive k at (4 ss + kq) VE of row r as one 16-byte load (row-major
+//    blocks whose rows are 16-byte multiples; the k order inside a block is free, A and B
+//    agree on it), four such loads in flight -- a block's first four issued before the next x
+//    block is staged (48x48 complex<float> n = 12: 203 -> 188 us) -- and applies them to all NT
+//    column tiles: the values are read once per group of NT tiles.  Blocks stored image-fastest (block_im_fast)
+//    are read as 16-element column runs, ragged tails element by element, never past the block;
+//  * rows of one or two strips split the k-steps of a block over 4 / 2 waves (kparts); the
+//    partial tiles are summed through LDS in wave order, so the result has one fixed order.
+// No LDS-DMA (no check_dma_lds), no atomics; every offset into v, x and y is 64-bit.
+template <typename E> struct alignas(16) BlkVec { E e[16 / sizeof(E)]; };
+
+template <typename R, bool CPLX, int NT>
+__global__ void __launch_bounds__(512) bsr_blk_mfma_kernel(const BsrArgs p, int yrow, int xrow, int nstrips,
+                                                           int kparts, int vec_ok) {
+    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    typedef typename BsrMfma<R>::acc_t acc_t;
+    typedef BlkVec<E> V;
+    constexpr int VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    E *xs = (E *)smem;
+    const E *__restrict__ v = (const E *)p.v;
+    const E *__restrict__ x = (const E *)p.x;
+    E *__restrict__ y = (E *)p.y;
+    const int bi = p.bi, bd = p.bd;
+    const int nss = (bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE; // k-steps of 4 VE
+    const int xbuf = kpad * XW;                                        // elements per x buffer
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long i = blockIdx.x, col0 = (long)blockIdx.y * XW;
+    const bool active = w < nstrips * kparts;
+    const int strip = w % nstrips, kp = w / nstrips;
+    const int ar = lane & 15, kq = lane >> 4;
+    const int arow = strip * 16 + ar;
+    const bool arow_ok = active && arow < bi;
+
+    // staging order: element e = outer * nin + inner, inner the fastest index of x (the rhs
+    // column for row-major x, else the domain row), walked by steps of the workgroup size
+    const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
+    const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
+    auto stage = [&](int j, int buf) {
+        const int dj = p.jj[j];
+        if (dj < 0) return;
+        E *dst = xs + buf * xbuf;
+        int in = in0, out = out0;
+        while (out < nout) {
+            E t[4];
+            int kk[4], cc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                kk[q] = xrow ? out : in;
+                cc[q] = xrow ? in : out;
+                const long col = col0 + cc[q];
+                t[q] = E{};
+                if (out < nout && kk[q] < bd && col < p.ncols)
+                    t[q] = xrow ? x[(long)(dj + kk[q]) * p.ldx + col] : x[(long)(dj + kk[q]) + col * p.ldx];
+                if (out >= nout) kk[q] = -1;
+                in += din;
+                out += dout;
+                if (in >= nin) {
+                    in -= nin;
+                    ++out;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
+        }
+    };
+    auto load_a = [&](const E *vb, int ss) {
+        V a;
+#pragma unroll
+        for (int t = 0; t < VE; ++t) a.e[t] = E{};
+        const int k0 = (ss * 4 + kq) * VE;
+        if (arow_ok && k0 < bd) {
+            if (!p.block_im_fast) {
+                const E *src = vb + (long)arow * bd + k0;
+                if (vec_ok && k0 + VE <= bd) {
+                    a = *(const V *)src;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < VE; ++t)
+                        if (k0 + t < bd) a.e[t] = src[t];
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < VE; ++t)
+                    if (k0 + t < bd) a.e[t] = vb[arow + (long)(k0 + t) * bi];
+            }
+        }
+        return a;
+    };
+    acc_t accR[NT], accI[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
+    auto apply = [&](const V &a, int ss, const E *xb) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const V b = *(const V *)(xb + ((ss * 4 + kq) * XW + nt * 16 + ar) * VE);
+#pragma unroll
+            for (int t = 0; t < VE; ++t) {
+                if constexpr (CPLX) {
+                    accR[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].x, accR[nt]);
+                    accI[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].y, accI[nt]);
+                    accR[nt] = BsrMfma<R>::mma(-a.e[t].y, b.e[t].y, accR[nt]);
+                    accI[nt] = BsrMfma<R>::mma(a.e[t].y, b.e[t].x, accI[nt]);
+                } else {
+                    accR[nt] = BsrMfma<R>::mma(a.e[t], b.e[t], accR[nt]);
+                }
+            }
+        }
+    };
+
+    const int jb = p.ii[i], je = p.ii[i + 1];
+    if (jb < je) stage(jb, 0);
+    __syncthreads();
+    for (int j = jb; j < je; ++j) {
+        const int buf = (j - jb) & 1;
+        const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
+        const E *vb = v + (long)j * bi * bd;
+        const E *xb = xs + buf * xbuf;
+        // the block's first U fragments are in flight while the next x block is staged
+        V a[U];
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) a[u] = load_a(vb, kp + u * kparts);
+        }
+        if (j + 1 < je) stage(j + 1, buf ^ 1);
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (kp + u * kparts < nss) apply(a[u], kp + u * kparts, xb);
+            for (int ss = kp + U * kparts; ss < nss; ss += U * kparts) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) a[u] = load_a(vb, ss + u * kparts);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (ss + u * kparts < nss) apply(a[u], ss + u * kparts, xb);
+            }
+        }
+        __syncthreads(); // buffer buf is free again, buffer buf ^ 1 is complete
+    }
+    if (kparts > 1) {
+        // the x buffers are dead (every path above ends in a barrier): partial tiles of the
+        // k-parts 1.. to LDS, summed by part 0 in part order
+        R *red = (R *)smem;
+        if (active && kp > 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    red[(((w * NT + nt) * NC + 0) * 4 + q) * 64 + lane] = accR[nt][q];
+                    if constexpr (CPLX) red[(((w * NT + nt) * NC + 1) * 4 + q) * 64 + lane] = accI[nt][q];
+                }
+        }
+        __syncthreads();
+        if (active && kp == 0) {
+            for (int k2 = 1; k2 < kparts; ++k2) {
+                const int w2 = strip + k2 * nstrips;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        accR[nt][q] += red[(((w2 * NT + nt) * NC + 0) * 4 + q) * 64 + lane];
+                        if constexpr (CPLX) accI[nt][q] += red[(((w2 * NT + nt) * NC + 1) * 4 + q) * 64 + lane];
+                    }
+            }
+        }
+    }
+    if (!active || kp != 0) return;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = strip * 16 + BsrMfma<R>::row(lane, q);
+            const long col = col0 + nt * 16 + ar;
+            if (row >= bi || col >= p.ncols) continue;
+            const long img = i * bi + row;
+            E *yp = yrow ? y + img * p.ldy + col : y + img + col * p.ldy;
+            E out;
+            if constexpr (CPLX)
+                out = Ops<E>::scale(E{accR[nt][q], accI[nt][q]}, p.alpha_re, p.alpha_im);
+            else
+                out = Ops<E>::scale(accR[nt][q], p.alpha_re, p.alpha_im);
+            *yp = p.add ? Ops<E>::add(*yp, out) : out;
+        }
+}
+
+/// false: not this shape (the generic kernel runs).  Limits: bi <= 128 (8 strips, one wave each),
+/// two x buffers of 16 columns within 64 KB of LDS (bd <= 128 for complex<double>, 256 for
+/// 8-byte and 512 for 4-byte elements), at most 65535 groups of NT column tiles.
+template <typename R, bool CPLX>
+bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    constexpr int ES = (int)sizeof(E), VE = 16 / ES;
+    const int nstrips = (a.bi + 15) / 16;
+    if (nstrips > 8 || a.block_rows >= (1L << 31)) return false;
+    const int nss = (a.bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE;
+    const int kparts = std::min(nstrips == 1 ? 4 : nstrips == 2 ? 2 : 1, nss);
+    const int nw = nstrips * kparts;
+    auto lds_of = [&](int nt) {
+        const long xb = 2L * kpad * nt * 16 * ES;
+        const long red = kparts > 1 ? (long)nw * nt * (CPLX ? 2 : 1) * 4 * 64 * (long)sizeof(R) : 0;
+        return std::max(xb, red);
+    };
+    // NT column tiles share the value fragments; within 32 KB of LDS where that keeps NT > 1
+    // (several workgroups per CU hide the value stream's latency)
+    int nt = a.ncols <= 16 ? 1 : a.ncols <= 32 ? 2 : 4;
+    while (nt > 1 && lds_of(nt) > 32768) nt /= 2;
+    const long lds = lds_of(nt);
+    if (lds > 65536) return false;
+    const long ngroups = (a.ncols + nt * 16 - 1) / (nt * 16);
+    if (ngroups > 65535) return false;
+    const int vec_ok = ((long)a.bd * ES) % 16 == 0 && ((size_t)a.v & 15) == 0 ? 1 : 0;
+    g_bsr_tune.last = 14;
+    KernelTimer timer("bsr", s);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
+                           yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
+    };
+    if (nt == 1) go(bsr_blk_mfma_kernel<R, CPLX, 1>);
+    else if (nt == 2) go(bsr_blk_mfma_kernel<R, CPLX, 2>);
+    else go(bsr_blk_mfma_kernel<R, CPLX, 4>);
+    SBX_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+template <typename E> bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    if constexpr (std::is_same<E, double2>::value) return launch_bsr_blk_mfma<double, true>(a, yrow, xrow, s);
+    else if constexpr (std::is_same<E, double>::value) return launch_bsr_blk_mfma<double, false>(a, yrow, xrow, s);
+    else if constexpr (std::is_same<E, float2>::value) return launch_bsr_blk_mfma<float, true>(a, yrow, xrow, s);
+    else return launch_bsr_blk_mfma<float, false>(a, yrow, xrow, s);
+}
+
 template <typename E>
 void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipStream_t s) {
     const long total = a.block_rows * a.bi * a.ncols;
@@ -1422,6 +1664,17 @@ void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipSt
         else
             launch_bsr_mfma<float, false, 12, 12>(a, nnz_per_row, yrow, xrow, s);
     }
+    // dense blocks from blk_min x blk_min on: bsr_blk_mfma_kernel where it was measured faster
+    // than the generic kernel by more than the round-to-round spread (8^4 9-point operators,
+    // complex<float> and complex<double>, profiles/bsr_blocks_measure.txt): 32x32 blocks and
+    // larger at any column count (1.15-8.7x), 24x24 from 4 columns (complex<double> n = 1: a
+    // tie), 16x16 from 12 columns (complex<double> n = 1 / 4: 0.75x / 0.93x); between the
+    // measured sizes the bound goes by the block's elements.  blk_mfma 2: no column bound
+    else if (g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
+             a.bd >= g_bsr_tune.blk_min &&
+             a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : a.bi * a.bd >= 24 * 24 ? 4 : 12) &&
+             launch_blk<E>(a, yrow, xrow, s))
+        return;
     else
         launch_layouts<E, 0, 0>(a, yrow, xrow, blocks, s);
 }

@@ -323,13 +323,20 @@ struct BsrTune {
                 ///< thread per block.  Default 1 | 2 | 8 (tools/bsr_bound.py NTS, warm, interleaved:
                 ///< 12x12 complex<double> 340 -> 328 us, complex<float> 179 -> 168 us, 3x3 n = 64
                 ///< 161 -> 158 us, n = 1 19.0 -> 18.2 us; the split-row kernel 34.4 -> 42.5 us: off)
+    int blk_mfma = 1; ///< dense blocks of at least blk_min x blk_min (the multigrid coarse operators) on
+                      ///< bsr_blk_mfma_kernel: 16-row strips of a block row on the matrix cores, the value
+                      ///< blocks as 16-byte loads, x staged once per workgroup (0 = the generic kernel; 1 = where it
+                      ///< was measured faster: blocks of 1024 elements and more at any column count, of
+                      ///< 576 and more from 4 rhs columns, smaller ones from 12; 2 = at any column count)
+    int blk_min = 16; ///< ... block image and domain sizes from this on (4..: lower for comparison runs)
     /// read-back ("bsr.last_kernel"; atomic: launches may come from several host threads): the form
     /// of the last launch -- 1 one thread per block (3x3), 2 split rows (3x3), 3 row chunks (3x3),
     /// 4 site tiles (3x3),
     /// 5 Kronecker on MFMA, 6 the same with packed column slots, 7 12x12 blocks by LDS-DMA, 8 the
     /// same with packed slots, 9 Kronecker spin first (VALU), 10 12x12 fragment gathers (9 blocks
     /// per row), 11 12x12 generic rows, 12 Kronecker spin first with XOR-partner spin rows,
-    /// 13 site tiles of 8 sites and 16 columns (3x3),
+    /// 13 site tiles of 8 sites and 16 columns (3x3), 14 dense blocks of blk_min and more on MFMA
+    /// (bsr_blk_mfma_kernel),
     /// 0 another kernel
     std::atomic<int> last{0};
 };
