@@ -628,7 +628,10 @@ void create_bsr(const PartitionItem<Ni> *pim, const Coor<Ni> &dimi, const Partit
 }
 
 /// create_kron_bsr (bsr.h:2476-2490): kronv[c] holds one volume(kronim) x volume(krondm) matrix
-/// per nonzero position of a block row; keep ii, jj, v and kronv allocated until destroy_bsr
+/// per nonzero position of a block row; keep ii, jj, v and kronv allocated until destroy_bsr.
+/// bsr_krylov contracts such an operator with either side: x with the domain labels gives A x,
+/// x with the image labels A^H x (the reference's local Kronecker operators throw "unsupported
+/// conjugation" for the latter, bsr.h:399, 1032); A^H reads v and kronv in place
 template <std::size_t Nd, std::size_t Ni, typename T>
 void create_kron_bsr(const PartitionItem<Ni> *pim, const Coor<Ni> &dimi,
                      const PartitionItem<Nd> *pdm, const Coor<Nd> &dimd, int ncomponents,

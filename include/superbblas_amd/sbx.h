@@ -115,7 +115,9 @@ int sbx_timings_report(char *buf, int len);
    output tiles and mirror the rest; 0 = off, the default), "gemm.loaders", "gemm.dma_spread", "gemm.skinny", "copy.nt", "copy.budget", "copy.run", "copy.max_elems", "copy.pair",
    "copy.order", "copy.trans", "copy.btrans", "bsr.variant", "bsr.row_max_cols", "bsr.split_max_cols",
    "bsr.split_cw", "bsr.split_jb", "bsr.split_ilv", "bsr.kron_mfma", "bsr.kron_mfma_min_cols",
-   "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.nt", "bsr.blk_pd", "bsr.blk_mfma" (dense blocks of
+   "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.kron_adj" (the adjoint of 3x3 x 4x4
+   Kronecker operators, x with the image labels: 1, the default, bsr_kron_adj_kernel; 0 the generic
+   adjoint kernel, 2 bsr_kron_adj_kernel without its LDS staging, both for comparison), "bsr.nt", "bsr.blk_pd", "bsr.blk_mfma" (dense blocks of
    "bsr.blk_min" x "bsr.blk_min" and more -- default 16, the multigrid coarse operators -- on the matrix-core
    kernel bsr_blk_mfma_kernel: 1, the default, where it was measured faster than the generic kernel -- blocks
    of 1024 elements and more at any rhs column count, of 576 and more from 4 columns, smaller ones from 12;
@@ -264,13 +266,20 @@ int sbx_create_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const
    blockImFast) per nonzero position of a block row; every block row must have the same number
    of nonzero blocks and no -1 domain coordinates (get_kron_indices, bsr.h:1485-1537).
    kronv must stay allocated until sbx_destroy_bsr.  bsr_krylov then prefers row-major x / y
-   with the Kronecker labels fastest: (D, d, C, kd) and (I, i, C, ki). */
+   with the Kronecker labels fastest: (D, d, C, kd) and (I, i, C, ki).  Both contraction sides
+   work, as for sbx_create_bsr: with the image labels on x, sbx_bsr_krylov computes
+   y = alpha A^H x (beyond the reference, whose local Kronecker operators throw "unsupported
+   conjugation", bsr.h:399, 1032); A^H reads v and kronv in place, conj-transposed, so it follows
+   changes made to them just as A does. */
 int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const int *pdm,
                         const int *dimd, int ncomponents, const int *blockim, const int *blockdm,
                         const int *kronim, const int *krondm, int blockImFast,
                         const int *const *ii, const int *const *jj, const void *const *v,
                         const void *const *kronv, const sbx_context *ctx, sbx_comm comm, int co,
                         sbx_bsr *bsrh, int session);
+/* bsr_krylov (bsr.h:2516-2543): x with the domain labels odm: y = alpha A x (+ beta y); x with
+   the image labels oim: y = alpha A^H x (+ beta y), y with the domain labels -- for operators of
+   sbx_create_bsr and of sbx_create_kron_bsr alike, with powers (okr), just_local and requests. */
 int sbx_bsr_krylov(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, const double *alpha,
                    const char *oim, const char *odm, const int *px, int ncomponents,
                    const char *ox, const int *fromx, const int *sizex, const int *dimx,

@@ -15,6 +15,10 @@
 //    them (bsr.h:1914-1928), and the local product runs kernels_bsr_kron.hip.
 //  * contracting with the image side (x has the image labels) applies A^H: a conj-transposed
 //    operator built on first use (make_transposed), whose overlapping image pieces are summed.
+//    For Kronecker operators A^H copies no values: per domain site of A it lists A's nonzeros
+//    pointing at the site, and the kernel reads A's own blocks and spin matrices conj-transposed
+//    (bsr_kron_adj_kernel; the reference's local Kronecker operators throw "unsupported
+//    conjugation" there, bsr.h:399, 1032).
 #include "plan.h"
 
 #include <algorithm>
@@ -47,6 +51,10 @@ struct BsrComp {
     void *kron_xor = nullptr;        // ... as diagonal + XOR partner (build_kron_terms)
     bool kron_terms_due = false;     // ... tables not built yet (built on the first launch that
                                      // asks for a spin-first kernel, bsr.kron_spin)
+    // the adjoint of a Kronecker operator A (make_transposed): v / kron are A's own arrays;
+    // adj_ptr [block_rows + 1] the row pointer over A's domain sites, adj_ent A's nonzero index
+    // k = I * nnz + mu of each entry, ascending within a site (nnz_per_row holds A's nnz)
+    int *adj_ptr = nullptr, *adj_ent = nullptr;
 };
 
 struct BsrOp {
@@ -76,6 +84,8 @@ struct BsrOp {
             if (c.kron_perm) (void)hipFree(c.kron_perm);
             if (c.kron_terms) (void)hipFree(c.kron_terms);
             if (c.kron_xor) (void)hipFree(c.kron_xor);
+            if (c.adj_ptr) (void)hipFree(c.adj_ptr);
+            if (c.adj_ent) (void)hipFree(c.adj_ent);
         }
     }
 };
@@ -445,9 +455,10 @@ BsrOp *bsr_create(int nd, int ni, int dtype, const std::vector<std::vector<Range
             build_kron_order(bc, ri.size, blocki, op->kroni);
             bc.kron_terms_due = true;
         }
+        // (the host pattern: the transposed operator is built from it)
+        bc.h_rowptr = std::move(rowptr);
+        bc.h_jj = std::move(hjj);
         if (!op->is_kron) {
-            bc.h_rowptr = std::move(rowptr);
-            bc.h_jj = std::move(hjj);
             if (bi == 3 && bd == 3 && bc.nnz_per_row == 9 && dtype == SBX_CDOUBLE) {
                 // (the kernels' LDS budgets: 16 sites x 8 columns up to 116 staged rows, 8 sites
                 // x 16 columns up to 80)
@@ -462,13 +473,18 @@ BsrOp *bsr_create(int nd, int ni, int dtype, const std::vector<std::vector<Range
 
 namespace {
 
-/// The conjugate transpose A^H of a (non-Kronecker) operator, for contractions with the image
-/// side of A (the reference's transSp: hipsparse bsrmm with CONJUGATE_TRANSPOSE,
-/// bsr.h:1001-1029, 1942): image partition = A's domain partition (which may overlap across
-/// components: the halos), domain partition = A's image partition, blocks conj-transposed and
-/// regrouped by block column.
+/// The conjugate transpose A^H of an operator, for contractions with the image side of A (the
+/// reference's transSp: hipsparse bsrmm with CONJUGATE_TRANSPOSE, bsr.h:1001-1029, 1942): image
+/// partition = A's domain partition (which may overlap across components: the halos), domain
+/// partition = A's image partition, blocks conj-transposed and regrouped by block column.
+/// Kronecker operators: a domain site of A is referenced by any number of nonzeros (halo sites
+/// by fewer; on a lattice of extent 2 both neighbours of a direction are one site), and the spin
+/// matrix of a nonzero goes with its slot mu in A's row -- so A^H is a row pointer over A's
+/// domain sites plus A's nonzero index k = I * nnz + mu per entry, and the kernel reads block k
+/// of A's values and matrix mu of A's spin matrices in place (no copy: 4 bytes per nonzero, and
+/// A^H follows the changes the caller makes to the values, as A does).  `a` owns the result
+/// (BsrOp::transposed), so A's arrays outlive it.
 BsrOp *make_transposed(const BsrOp &a) {
-    if (a.is_kron) throw Error("bsr_krylov: contracting with the image space of a Kronecker operator is not supported");
     std::unique_ptr<BsrOp> t(new BsrOp());
     t->nd = a.ni;
     t->ni = a.nd;
@@ -479,6 +495,7 @@ BsrOp *make_transposed(const BsrOp &a) {
     t->blockd = a.blocki;
     t->kroni = a.krond;
     t->krond = a.kroni;
+    t->is_kron = a.is_kron;
     t->block_im_fast = !a.block_im_fast; // the same block storage read transposed
     t->nprocs = a.nprocs;
     t->rank = a.rank;
@@ -499,7 +516,41 @@ BsrOp *make_transposed(const BsrOp &a) {
             }
     const long bi = volume(a.blocki), bd = volume(a.blockd);
     const std::size_t es = dtype_size(a.dtype);
-    for (int c = 0; c < (int)a.comps.size(); ++c) {
+    const long kd = volume(a.krond);
+    for (int c = 0; a.is_kron && c < (int)a.comps.size(); ++c) {
+        const BsrComp &ac = a.comps[c];
+        BsrComp bc;
+        bc.dev = ac.dev;
+        const long nsd = volume(a.pd[a.rank][c].size) / std::max(1L, bd * kd); // A's domain sites
+        if (ac.block_rows == 0 || nsd == 0) {
+            t->comps.push_back(bc);
+            continue;
+        }
+        bc.block_rows = nsd;
+        bc.x_rows = ac.block_rows * bi; // A's image sites x bi: the rows of A^H's x
+        bc.nnz_per_row = ac.nnz_per_row;
+        bc.v = ac.v;
+        bc.kron = ac.kron;
+        // counting sort of A's nonzeros by domain site, k ascending within a site: a fixed
+        // summation order; a site nothing points at keeps an empty row (its y is still written)
+        const std::vector<int> &jj = ac.h_jj;
+        const long nnz = ac.h_rowptr.back();
+        std::vector<int> ptr(nsd + 1, 0), ent(std::max(nnz, 1L));
+        for (long k = 0; k < nnz; ++k) {
+            if (jj[k] < 0 || jj[k] >= nsd) throw Error("kron bsr: internal error (domain site)");
+            ++ptr[jj[k] + 1];
+        }
+        for (long q = 0; q < nsd; ++q) ptr[q + 1] += ptr[q];
+        std::vector<int> pos(ptr.begin(), ptr.end() - 1);
+        for (long k = 0; k < nnz; ++k) ent[pos[jj[k]]++] = (int)k;
+        set_device(bc.dev);
+        SBX_HIP_CHECK(hipMalloc(&bc.adj_ptr, sizeof(int) * (nsd + 1)));
+        SBX_HIP_CHECK(hipMalloc(&bc.adj_ent, sizeof(int) * ent.size()));
+        SBX_HIP_CHECK(hipMemcpy(bc.adj_ptr, ptr.data(), sizeof(int) * (nsd + 1), hipMemcpyHostToDevice));
+        SBX_HIP_CHECK(hipMemcpy(bc.adj_ent, ent.data(), sizeof(int) * ent.size(), hipMemcpyHostToDevice));
+        t->comps.push_back(std::move(bc));
+    }
+    for (int c = 0; !a.is_kron && c < (int)a.comps.size(); ++c) {
         const BsrComp &ac = a.comps[c];
         BsrComp bc;
         bc.dev = ac.dev;
@@ -646,7 +697,11 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
         throw Error("Unsupported to contract dense input tensor with domain and image dimensions "
                     "of the sparse tensor");
     if (x_image) {
-        if (!op.transposed) op.transposed.reset(make_transposed(op));
+        {
+            static std::mutex mu; // (one host thread builds it)
+            std::lock_guard<std::mutex> lock(mu);
+            if (!op.transposed) op.transposed.reset(make_transposed(op));
+        }
         return bsr_krylov(*op.transposed, alpha, od, oi, x_in, fromx, sizex, beta, y_in, fromy,
                           sizey, okr, comm_in, just_local, deferred);
     }
@@ -921,6 +976,8 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
                     }
                     d.kron_terms = bc.kron_terms;
                     d.kron_xor = bc.kron_xor;
+                    d.adj_ptr = bc.adj_ptr;
+                    d.adj_ent = bc.adj_ent;
                     launch_bsr_kron(d, bc.dev);
                 } else {
                     launch_bsr(d, bc.dev);

@@ -447,6 +447,7 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "bsr.kron_xlds") g_bsr_tune.kron_xlds = (int)value;
         else if (k == "bsr.kron_ylds") g_bsr_tune.kron_ylds = (int)value;
         else if (k == "bsr.kron_spin") g_bsr_tune.kron_spin = (int)value;
+        else if (k == "bsr.kron_adj") g_bsr_tune.kron_adj = (int)value;
         else if (k == "bsr.kron_spin_min_cols") g_bsr_tune.kron_spin_min_cols = (long)value;
         else if (k == "bsr.kron_order") g_bsr_tune.kron_order = (int)value;
         else if (k == "bsr.nt") g_bsr_tune.nt = (int)value;
@@ -522,6 +523,7 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "bsr.kron_xlds") *value = g_bsr_tune.kron_xlds;
         else if (k == "bsr.kron_ylds") *value = g_bsr_tune.kron_ylds;
         else if (k == "bsr.kron_spin") *value = g_bsr_tune.kron_spin;
+        else if (k == "bsr.kron_adj") *value = g_bsr_tune.kron_adj;
         else if (k == "bsr.kron_spin_min_cols") *value = g_bsr_tune.kron_spin_min_cols;
         else if (k == "bsr.kron_order") *value = g_bsr_tune.kron_order;
         else if (k == "bsr.nt") *value = g_bsr_tune.nt;

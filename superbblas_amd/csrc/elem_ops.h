@@ -19,6 +19,7 @@ template <> struct Ops<double2> {
     static __device__ __forceinline__ double2 add(double2 a, double2 b) {
         return double2{a.x + b.x, a.y + b.y};
     }
+    static __device__ __forceinline__ double2 conj(double2 a) { return double2{a.x, -a.y}; }
     static __device__ __forceinline__ bool nonzero(double2 a) { return a.x != 0 || a.y != 0; }
 };
 template <> struct Ops<float2> {
@@ -32,6 +33,7 @@ template <> struct Ops<float2> {
     static __device__ __forceinline__ float2 add(float2 a, float2 b) {
         return float2{a.x + b.x, a.y + b.y};
     }
+    static __device__ __forceinline__ float2 conj(float2 a) { return float2{a.x, -a.y}; }
     static __device__ __forceinline__ bool nonzero(float2 a) { return a.x != 0 || a.y != 0; }
 };
 template <> struct Ops<double> {
@@ -39,6 +41,7 @@ template <> struct Ops<double> {
     static __device__ __forceinline__ double fma(double a, double b, double c) { return c + a * b; }
     static __device__ __forceinline__ double scale(double v, double ar, double) { return ar * v; }
     static __device__ __forceinline__ double add(double a, double b) { return a + b; }
+    static __device__ __forceinline__ double conj(double a) { return a; }
     static __device__ __forceinline__ bool nonzero(double a) { return a != 0; }
 };
 template <> struct Ops<float> {
@@ -48,6 +51,7 @@ template <> struct Ops<float> {
         return (float)ar * v;
     }
     static __device__ __forceinline__ float add(float a, float b) { return a + b; }
+    static __device__ __forceinline__ float conj(float a) { return a; }
     static __device__ __forceinline__ bool nonzero(float a) { return a != 0; }
 };
 

@@ -1003,7 +1003,271 @@ __global__ void __launch_bounds__(256) bsr_kron_xor_kernel(const KronArgs p) {
         }
 }
 
+// The adjoint, x with the image labels of A (the reference's local Kronecker operators throw
+// "unsupported conjugation" there, bsr.h:399, 1032): for every domain site J of the component
+//   y(J, d, n, b) = alpha * sum_{k : J(k) = J} sum_a conj(K_mu(a, b)) sum_i conj(U_k(i, d)) x(I, i, n, a)
+// with k = I * nnz + mu A's nonzero index.  A site is pointed at by any number of nonzeros (halo
+// sites by fewer; none at all is possible), so A^H is a row pointer over the sites and a list of
+// k per site (bsr.cpp make_transposed), ascending: a fixed summation order.  The values are A's
+// own arrays, block k and matrix mu read conj-transposed in place; no atomics; every offset
+// into v, x and y is 64-bit.
+struct KronAdjArgs {
+    long sites; ///< A's domain sites of the component: the rows of A^H
+    int nnz;    ///< A's nonzero blocks per block row (k = I * nnz + mu)
+    int bi, bd, ki, kd; ///< A's block and Kronecker sizes (image, domain)
+    const int *ptr; ///< [sites + 1] first entry of each site
+    const int *ent; ///< A's nonzero index of each entry
+    const void *v;
+    const void *kron;
+    int block_im_fast; ///< A's
+    const void *x; ///< (A's block row, bi, ncols, ki)
+    void *y;       ///< (site, bd, ncols, kd)
+    long ncols;
+    double alpha_re, alpha_im;
+    int add;
+};
+
+/// Entries staged per pass of bsr_kron_adj_kernel, and the sites of a workgroup: 16 sites of a
+/// 9-point stencil are 144 entries, one pass (a pass serves only the sites whose entries it
+/// holds, the other lanes wait: with 128 entries for 21 sites of 12 columns every lane sat out
+/// one of two passes, 373 us against 182 us for the forward product).  Staged from this many
+/// columns (16^4 sites, staged / not, us: complex<double> n = 4 115 / 81, 12 253 / 220, 16 276 /
+/// 266, 32 517 / 517, 64 957 / 979; complex<float> 4 73 / 58, 16 149 / 148, 32 296 / 308)
+constexpr int KRON_ADJ_CHUNK = 160, KRON_ADJ_SITES = 16, KRON_ADJ_STAGE_COLS = 32;
+
+/// A workgroup owns `S` consecutive sites x up to 256 columns (cpg columns per site), one thread
+/// per (site, column) keeping its BD * KD outputs in registers.  STAGE (from KRON_ADJ_STAGE_COLS
+/// columns): the workgroup's entries are one contiguous run of the entry list; their color blocks
+/// are gathered into LDS conj-transposed, KRON_ADJ_CHUNK entries a pass (coalesced 16-byte pieces
+/// of the 144-byte blocks, instead of every lane of a site fetching the same blocks through L1),
+/// and read back as broadcasts.  With fewer columns too few lanes share a site for the pass and
+/// its barriers to pay: each lane reads its blocks itself.  The spin matrices sit in LDS conj-transposed in both forms,
+/// since the mu of an entry differs from site to site (a wave spanning several sites: no scalar
+/// operand).  Per entry a lane reads the BI * KI x values of (I, ., column, .) -- consecutive
+/// lanes consecutive columns, contiguous KI-element pieces -- one entry ahead, does the color
+/// product t(d, a) = sum_i conj(U(i, d)) x(i, a), then the spin product
+/// acc(d, b) += sum_a conj(K(a, b)) t(d, a), skipping the zeros of K.
+template <typename E, int BI, int BD, int KI, int KD, bool STAGE>
+__global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, int S, int cpg) {
+    extern __shared__ __attribute__((aligned(16))) char smem_a[];
+    constexpr int BLK = BI * BD, KK = KI * KD, CH = STAGE ? KRON_ADJ_CHUNK : 0;
+    E *Us = (E *)smem_a; // [CH][BD][BI] conj(U(i, d))
+    E *Ks = Us + CH * BLK; // [nnz][KD][KI] conj(K(a, b))
+    const int nth = (int)blockDim.x;
+    const E *__restrict__ v = (const E *)p.v;
+    const E *__restrict__ kron = (const E *)p.kron;
+    const E *__restrict__ x = (const E *)p.x;
+    E *__restrict__ y = (E *)p.y;
+    const int tid = (int)threadIdx.x;
+    const long r0 = (long)blockIdx.x * S;
+    const int nrows = (int)std::min<long>(S, p.sites - r0);
+    for (int e = tid; e < p.nnz * KK; e += nth) {
+        const int mu = e / KK, w = e - mu * KK, b = w / KI, a = w - b * KI;
+        Ks[e] = Ops<E>::conj(kron[(long)mu * KK + (p.block_im_fast ? a + b * KI : a * KD + b)]);
+    }
+    const int sl = tid / cpg;
+    const long c = (long)blockIdx.y * cpg + tid % cpg;
+    const bool live = sl < nrows && c < p.ncols;
+    const long r = r0 + (live ? sl : 0);
+    const int e0 = p.ptr[r0], e1 = p.ptr[r0 + nrows]; // the workgroup's entries
+    const int lo = live ? p.ptr[r] : 0, hi = live ? p.ptr[r + 1] : 0; // the lane's
+    const long xrow = p.ncols * KI;
+    const E *xc = x + c * KI;
+    E acc[BD][KD];
+#pragma unroll
+    for (int d = 0; d < BD; ++d)
+#pragma unroll
+        for (int b = 0; b < KD; ++b) acc[d][b] = Ops<E>::zero();
+    auto load_x = [&](int k, E (&xo)[BI][KI]) {
+        const E *xs = xc + (long)(k / p.nnz) * BI * xrow;
+#pragma unroll
+        for (int i = 0; i < BI; ++i)
+#pragma unroll
+            for (int a = 0; a < KI; ++a) xo[i][a] = xs[i * xrow + a];
+    };
+    if constexpr (!STAGE) __syncthreads(); // the spin matrices
+    const int ustep = STAGE ? CH : std::max(e1 - e0, 1); // (not staged: one pass over the lane's entries)
+    for (int base = e0; base < e1; base += ustep) {
+        const int n = std::min(ustep, e1 - base);
+        if constexpr (STAGE) {
+            __syncthreads(); // the previous pass is consumed
+            for (int t = tid; t < n * BLK; t += nth) {
+                const int q = t / BLK, w = t - q * BLK, d = w / BI, i = w - d * BI;
+                const long k = p.ent[base + q];
+                Us[t] = Ops<E>::conj(v[k * BLK + (p.block_im_fast ? i + d * BI : i * BD + d)]);
+            }
+            __syncthreads();
+        }
+        const int a0 = std::max(lo, base), a1 = std::min(hi, base + n);
+        if (a0 >= a1) continue;
+        int k = p.ent[a0];
+        E xa[BI][KI];
+        load_x(k, xa);
+#pragma unroll 1
+        for (int e = a0; e < a1; ++e) {
+            const int mu = k % p.nnz;
+            E ug[BD][BI]; // not staged: the lane's own copy of the block
+            if constexpr (!STAGE) {
+                const E *ub = v + (long)k * BLK;
+#pragma unroll
+                for (int d = 0; d < BD; ++d)
+#pragma unroll
+                    for (int i = 0; i < BI; ++i)
+                        ug[d][i] = Ops<E>::conj(ub[p.block_im_fast ? i + d * BI : i * BD + d]);
+            }
+            E xb[BI][KI];
+            if (e + 1 < a1) {
+                k = p.ent[e + 1];
+                load_x(k, xb);
+            }
+            const E *U = Us + (e - base) * BLK;
+            const E *K = Ks + mu * KK;
+            // color: t(d, a) = sum_i conj(U(i, d)) x(i, a)
+            E t[BD][KI];
+#pragma unroll
+            for (int d = 0; d < BD; ++d)
+#pragma unroll
+                for (int a = 0; a < KI; ++a) t[d][a] = Ops<E>::zero();
+#pragma unroll
+            for (int i = 0; i < BI; ++i)
+#pragma unroll
+                for (int d = 0; d < BD; ++d) {
+                    const E u = STAGE ? U[d * BI + i] : ug[d][i];
+#pragma unroll
+                    for (int a = 0; a < KI; ++a) t[d][a] = Ops<E>::fma(u, xa[i][a], t[d][a]);
+                }
+            // spin: acc(d, b) += sum_a conj(K(a, b)) t(d, a)
+#pragma unroll
+            for (int b = 0; b < KD; ++b)
+#pragma unroll
+                for (int a = 0; a < KI; ++a) {
+                    const E kk = K[b * KI + a];
+                    if (!Ops<E>::nonzero(kk)) continue;
+#pragma unroll
+                    for (int d = 0; d < BD; ++d) acc[d][b] = Ops<E>::fma(kk, t[d][a], acc[d][b]);
+                }
+            if (e + 1 < a1) {
+#pragma unroll
+                for (int i = 0; i < BI; ++i)
+#pragma unroll
+                    for (int a = 0; a < KI; ++a) xa[i][a] = xb[i][a];
+            }
+        }
+    }
+    if (!live) return;
+    E *ys = y + (r * BD * p.ncols + c) * KD;
+#pragma unroll
+    for (int d = 0; d < BD; ++d)
+#pragma unroll
+        for (int b = 0; b < KD; ++b) {
+            E o = Ops<E>::scale(acc[d][b], p.alpha_re, p.alpha_im);
+            if (p.add) o = Ops<E>::add(o, ys[d * p.ncols * KD + b]);
+            ys[d * p.ncols * KD + b] = o;
+        }
+}
+
+/// Any block / Kronecker sizes: one thread per output element (site, d, column, b)
+template <typename E>
+__global__ void __launch_bounds__(256) bsr_kron_adj_generic_kernel(const KronAdjArgs p) {
+    const E *__restrict__ v = (const E *)p.v;
+    const E *__restrict__ kron = (const E *)p.kron;
+    const E *__restrict__ x = (const E *)p.x;
+    E *__restrict__ y = (E *)p.y;
+    const long total = p.sites * p.bd * p.ncols * p.kd;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
+        const int b = (int)(idx % p.kd);
+        long t = idx / p.kd;
+        const long c = t % p.ncols;
+        t /= p.ncols;
+        const int d = (int)(t % p.bd);
+        const long r = t / p.bd;
+        E acc = Ops<E>::zero();
+        for (int e = p.ptr[r]; e < p.ptr[r + 1]; ++e) {
+            const long k = p.ent[e];
+            const long I = k / p.nnz, mu = k - I * p.nnz;
+            const E *xs = x + (I * p.bi * p.ncols + c) * p.ki;
+            const E *K = kron + mu * p.ki * p.kd;
+            const E *U = v + k * p.bi * p.bd;
+            for (int a = 0; a < p.ki; ++a) {
+                const E kk = p.block_im_fast ? K[a + b * p.ki] : K[a * p.kd + b];
+                if (!Ops<E>::nonzero(kk)) continue;
+                E s = Ops<E>::zero();
+                for (int i = 0; i < p.bi; ++i) {
+                    const E u = p.block_im_fast ? U[i + d * p.bi] : U[i * p.bd + d];
+                    s = Ops<E>::fma(Ops<E>::conj(u), xs[i * p.ncols * p.ki + a], s);
+                }
+                acc = Ops<E>::fma(Ops<E>::conj(kk), s, acc);
+            }
+        }
+        E o = Ops<E>::scale(acc, p.alpha_re, p.alpha_im);
+        if (p.add) o = Ops<E>::add(o, y[idx]);
+        y[idx] = o;
+    }
+}
+
 constexpr long KRON_LDS_BYTES = 64 * 1024;
+
+template <typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream_t s) {
+    KernelTimer timer("bsr", s);
+    if (g_bsr_tune.kron_adj && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4) {
+        const int cpg = (int)std::min<long>(a.ncols, 256);
+        const bool stage = a.ncols >= KRON_ADJ_STAGE_COLS && g_bsr_tune.kron_adj != 2;
+        const int S = std::min(256 / cpg, stage ? KRON_ADJ_SITES : 256);
+        const int nth = (S * cpg + 63) / 64 * 64; // whole waves, at most 256 threads
+        const long gx = (a.sites + S - 1) / S, gy = (a.ncols + cpg - 1) / cpg;
+        const long lds = (long)((stage ? KRON_ADJ_CHUNK * 9 : 0) + (long)a.nnz * 16) * (long)sizeof(E);
+        if (lds <= KRON_LDS_BYTES && gx < (1L << 31) && gy < 65536) {
+            g_bsr_tune.last = 15;
+            if (stage)
+                hipLaunchKernelGGL((bsr_kron_adj_kernel<E, 3, 3, 4, 4, true>), dim3((unsigned)gx, (unsigned)gy),
+                                   dim3(nth), (size_t)lds, s, a, S, cpg);
+            else
+                hipLaunchKernelGGL((bsr_kron_adj_kernel<E, 3, 3, 4, 4, false>), dim3((unsigned)gx, (unsigned)gy),
+                                   dim3(nth), (size_t)lds, s, a, S, cpg);
+            SBX_HIP_CHECK(hipGetLastError());
+            return;
+        }
+    }
+    g_bsr_tune.last = 16;
+    const long total = a.sites * a.bd * a.ncols * a.kd;
+    const long blocks = std::min((total + 255) / 256, 65536L);
+    hipLaunchKernelGGL((bsr_kron_adj_generic_kernel<E>), dim3(blocks), dim3(256), 0, s, a);
+    SBX_HIP_CHECK(hipGetLastError());
+}
+
+/// The adjoint of a Kronecker operator: the descriptor speaks of A^H (BsrDesc), the kernels of A
+void launch_bsr_kron_adj(const BsrDesc &d, int device) {
+    if (d.num_nnz_per_row <= 0 || !d.kron || !d.adj_ent || !d.x_row_major || !d.y_row_major)
+        throw Error("kron bsr: internal error (adjoint layout or pattern)");
+    set_device(device);
+    g_bsr_tune.last = 0;
+    KronAdjArgs a{};
+    a.sites = d.block_rows;
+    a.nnz = d.num_nnz_per_row;
+    a.bi = d.bd;
+    a.bd = d.bi;
+    a.ki = d.kd;
+    a.kd = d.ki;
+    a.ptr = d.adj_ptr;
+    a.ent = d.adj_ent;
+    a.v = d.v;
+    a.kron = d.kron;
+    a.block_im_fast = d.block_im_fast ? 0 : 1;
+    a.x = d.x;
+    a.y = d.y;
+    a.ncols = d.ncols;
+    a.alpha_re = d.alpha.re;
+    a.alpha_im = d.alpha.im;
+    a.add = d.add ? 1 : 0;
+    hipStream_t s = get_stream(device);
+    switch (d.t) {
+    case SBX_CDOUBLE: return launch_kron_adj_typed<double2>(a, s);
+    case SBX_CFLOAT: return launch_kron_adj_typed<float2>(a, s);
+    case SBX_DOUBLE: return launch_kron_adj_typed<double>(a, s);
+    case SBX_FLOAT: return launch_kron_adj_typed<float>(a, s);
+    default: throw Error("kron bsr: unsupported type");
+    }
+}
 
 template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
@@ -1122,6 +1386,7 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
 
 void launch_bsr_kron(const BsrDesc &d, int device) {
     if (d.block_rows == 0 || d.ncols == 0) return;
+    if (d.adj_ptr) return launch_bsr_kron_adj(d, device);
     if (d.num_nnz_per_row <= 0 || !d.kron || !d.x_row_major || !d.y_row_major)
         throw Error("kron bsr: internal error (layout or pattern)");
     set_device(device);

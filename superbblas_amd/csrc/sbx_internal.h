@@ -311,6 +311,10 @@ struct BsrTune {
                                  ///< default: n = 12 142 us against 180 / 190)
     long kron_spin_min_cols = 8; ///< ... from this many rhs columns (at least 8)
     int kron_order = 1;          ///< ... rows in the operator's XCD order (bsr.cpp build_kron_order)
+    int kron_adj = 1;            ///< adjoint of a Kronecker operator (x with the image labels), 3x3 x 4x4: 1 = a thread
+                                 ///< per (domain site, column) with the site's blocks staged in LDS
+                                 ///< from 32 columns (bsr_kron_adj_kernel), 0 = the generic kernel (one thread per
+                                 ///< output element), 2 = bsr_kron_adj_kernel never staging (for comparison)
     int blk_pd = 1; ///< 12x12 blocks by LDS-DMA: blocks in flight ahead of the one in use (1..3)
     int tile = 0;   ///< 9-point 3x3 complex<double> operators, row-major x and y: site tiles with
                     ///< their halo staged in LDS (bsr_ell9_tile_kernel) ... 1: 16-site tiles, slices
@@ -336,7 +340,8 @@ struct BsrTune {
     /// same with packed slots, 9 Kronecker spin first (VALU), 10 12x12 fragment gathers (9 blocks
     /// per row), 11 12x12 generic rows, 12 Kronecker spin first with XOR-partner spin rows,
     /// 13 site tiles of 8 sites and 16 columns (3x3), 14 dense blocks of blk_min and more on MFMA
-    /// (bsr_blk_mfma_kernel),
+    /// (bsr_blk_mfma_kernel), 15 Kronecker adjoint, a thread per (domain site, column)
+    /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element,
     /// 0 another kernel
     std::atomic<int> last{0};
 };
@@ -413,6 +418,12 @@ struct BsrDesc {
     const int *kron_perm = nullptr; ///< block row per row slot in the XCD order (nullptr: none)
     const void *kron_terms = nullptr; ///< spin rows as two terms (nullptr: a row has more nonzeros)
     const void *kron_xor = nullptr;   ///< spin rows as diagonal + XOR partner (nullptr: not of that form)
+    // The adjoint of a Kronecker operator A (nullptr: a forward operator): block_rows are A's
+    // domain sites, bi / ki A's domain and bd / kd A's image sizes, block_im_fast the opposite
+    // of A's, v / kron A's own arrays and num_nnz_per_row A's count; adj_ptr [block_rows + 1]
+    // the row pointer over the sites, adj_ent A's nonzero index k = I * nnz + mu per entry
+    // (ii / jj unused); x is (A's block row, A's bi, ncols, A's ki), y (site, A's bd, ncols, A's kd)
+    const int *adj_ptr = nullptr, *adj_ent = nullptr;
     // site tiles of 3x3 9-point operators (bsr.cpp build_tile_schedule): [0] 16-site tiles (the
     // 8-column kernel), [1] 8-site tiles (the 16-column kernel); rows == nullptr: none
     TileSched tiles[2];
