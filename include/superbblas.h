@@ -606,6 +606,13 @@ void contraction(T alpha, const PartitionItem<Nd0> *p0, const Coor<Nd0> &from0,
 
 // ---- BSR operator (bsr.h:2440-2580, 2286-2398) ----
 
+/// Mixed precision (an extension; the reference's bsr_krylov is one T throughout): an operator
+/// of create_bsr<Nd, Ni, float> or <Nd, Ni, std::complex<float>> may be contracted by
+/// bsr_krylov<Nd, Ni, Nx, Ny, T> with T the double counterpart (double, std::complex<double>) on
+/// the same handle.  Every value is converted to double exactly where it is read -- in place, in
+/// the caller's array, no converted copy is kept -- and products, sums, alpha, beta and y are
+/// double: the result is the product of the up-converted operator with x.  Every other pair of
+/// types, and any type difference on an operator of create_kron_bsr, throws as before.
 template <std::size_t Nd, std::size_t Ni, typename T>
 void create_bsr(const PartitionItem<Ni> *pim, const Coor<Ni> &dimi, const PartitionItem<Nd> *pdm,
                 const Coor<Nd> &dimd, int ncomponents, const Coor<Ni> &blockim,

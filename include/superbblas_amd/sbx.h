@@ -122,10 +122,17 @@ int sbx_timings_report(char *buf, int len);
    kernel bsr_blk_mfma_kernel: 1, the default, where it was measured faster than the generic kernel -- blocks
    of 1024 elements and more at any rhs column count, of 576 and more from 4 columns, smaller ones from 12;
    2 at any column count; 0 the generic kernel; 3x3, 12x12 and Kronecker operators keep their kernels),
+   "bsr.mixed" (a float / complex<float> operator applied to double / complex<double> vectors, see
+   sbx_bsr_krylov: 1, the default, the dense blocks that "bsr.blk_mfma", "bsr.blk_min" and "bsr.variant" admit
+   on the mixed matrix-core kernel bsr_blk_mfma_mixed_kernel where it was measured faster than the generic
+   mixed kernel -- blocks of 1024 elements and more at any rhs column count, smaller ones from 4 columns;
+   "bsr.blk_mfma" 2 at any column count; 0 every mixed product on the generic mixed kernel; never a converted copy),
    "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
-   last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel), "dist.peer_copies",
+   last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel; 16 with "bsr.last_mixed" 1 =
+   bsr_blk_mfma_mixed_kernel, 0 with it = the generic mixed kernel), "bsr.last_mixed" (1 when the last BSR
+   launch read values of a narrower type than its vectors, else 0), "dist.peer_copies",
    "copy.last_pair", "gemm.last_herm" (tiles per batch entry the last GEMM launch mirrored instead
    of computed; 0 = a full product), "gemm.last_lean" (1 when the last GEMM launch took the lean form of
    the complex<double> 128x128x16 kernel, key "gemm.lean", on by default and bit-identical to the generic
@@ -279,7 +286,17 @@ int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, 
                         sbx_bsr *bsrh, int session);
 /* bsr_krylov (bsr.h:2516-2543): x with the domain labels odm: y = alpha A x (+ beta y); x with
    the image labels oim: y = alpha A^H x (+ beta y), y with the domain labels -- for operators of
-   sbx_create_bsr and of sbx_create_kron_bsr alike, with powers (okr), just_local and requests. */
+   sbx_create_bsr and of sbx_create_kron_bsr alike, with powers (okr), just_local and requests.
+   t is the type of x and y: the operator's, or -- mixed precision, an extension (the reference's
+   bsr_krylov is one type throughout), for operators of sbx_create_bsr only -- SBX_DOUBLE for an
+   SBX_FLOAT operator and SBX_CDOUBLE for an SBX_CFLOAT one.  The values are then read in place
+   in the operator's type and converted to double (exactly) where they are loaded; products,
+   sums, alpha, beta and y are double, so the result is the product of the up-converted operator
+   with x, at half the operator's memory and value traffic.  No converted copy is made: values
+   changed after one product show in the next.  Both contraction sides (A^H through the
+   transposed operator, which stays in the operator's type), any layout and partition,
+   temporaries, powers, just_local, requests and host contexts work as for one type.  Every other
+   difference of types fails with the same errors as before and leaves y untouched. */
 int sbx_bsr_krylov(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, const double *alpha,
                    const char *oim, const char *odm, const int *px, int ncomponents,
                    const char *ox, const int *fromx, const int *sizex, const int *dimx,

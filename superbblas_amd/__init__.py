@@ -745,7 +745,12 @@ def bsr_krylov(alpha, bsr: BSR, oim: str, odm: str, px, ox: str, fromx, sizex, d
                comm: Optional[Comm] = None, request: bool = False, just_local: bool = False):
     """y = alpha * A x (+ beta y) (bsr.h:2516-2543; MPI form 2352-2383).  just_local: only this
     rank's part, no exchange.  request=True: returns a Request when the halo exchange is left in
-    flight (the local product runs at its wait()), else None."""
+    flight (the local product runs at its wait()), else None.
+
+    The type is that of vx / vy.  Mixed precision (an extension): an operator of create_bsr in
+    float32 / complex64 may be applied to float64 / complex128 vx and vy; its values are read in
+    place, widened exactly where they are loaded, and the product is computed and written in
+    double (no converted copy is kept).  Any other difference of types raises."""
     nx, ny = len(ox), len(oy)
     nc = len(vx)
     t = _dtype_of(list(vx) + list(vy))

@@ -754,8 +754,15 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
         if ((op.blocki[i] > 1 && op.blocki[i] != op.dimi[i]) ||
             (op.kroni[i] > 1 && op.kroni[i] != op.dimi[i]))
             throw Error("Still not supported partially blocking a dimension");
-    if (x.dtype != op.dtype || y.dtype != op.dtype) throw Error("bsr_krylov: type mismatch");
-    const int dtype = op.dtype;
+    // x and y have the operator's type, or -- an extension, not for Kronecker operators -- a
+    // single-precision operator is applied to vectors of its double counterpart: the values are
+    // read in place and widened at the load, everything else (temporaries, halo exchange,
+    // copies) is in x's type
+    const bool mixed = !op.is_kron && ((op.dtype == SBX_FLOAT && x.dtype == SBX_DOUBLE) ||
+                                       (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE));
+    if (x.dtype != y.dtype || (x.dtype != op.dtype && !mixed))
+        throw Error("bsr_krylov: type mismatch");
+    const int dtype = x.dtype;
     const std::size_t es = dtype_size(dtype);
     const int bi = (int)volume(op.blocki), bd = (int)volume(op.blockd);
 
@@ -938,6 +945,8 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
                 if (bc.block_rows == 0) continue;
                 BsrDesc d;
                 d.t = dtype;
+                d.tv = op.dtype;
+                g_bsr_tune.last_mixed = d.tv != d.t ? 1 : 0;
                 d.block_rows = bc.block_rows;
                 d.bi = bi;
                 d.bd = bd;

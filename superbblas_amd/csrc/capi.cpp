@@ -455,6 +455,7 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "bsr.blk_pd") g_bsr_tune.blk_pd = (int)value;
         else if (k == "bsr.blk_mfma") g_bsr_tune.blk_mfma = (int)value;
         else if (k == "bsr.blk_min") g_bsr_tune.blk_min = (int)value;
+        else if (k == "bsr.mixed") g_bsr_tune.mixed = (int)value;
         else if (k == "bsr.tile") g_bsr_tune.tile = (int)value;
         else if (k == "bsr.tile_min_cols") g_bsr_tune.tile_min_cols = value;
         else if (k == "gemm.m3") g_gemm_tune.m3 = (int)value;
@@ -533,7 +534,9 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "bsr.blk_min") *value = g_bsr_tune.blk_min;
         else if (k == "bsr.tile") *value = g_bsr_tune.tile;
         else if (k == "bsr.tile_min_cols") *value = g_bsr_tune.tile_min_cols;
+        else if (k == "bsr.mixed") *value = g_bsr_tune.mixed;
         else if (k == "bsr.last_kernel") *value = g_bsr_tune.last;
+        else if (k == "bsr.last_mixed") *value = g_bsr_tune.last_mixed;
         else if (k == "gemm.m3") *value = g_gemm_tune.m3;
         else if (k == "gemm.splits") *value = g_gemm_tune.splits;
         else if (k == "gemm.t48") *value = g_gemm_tune.t48;
@@ -1088,7 +1091,11 @@ int sbx_bsr_krylov_req(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, cons
     return guard([&] {
         check_session(session);
         if (!bsrh || !bsrh->op) throw Error("bsr_krylov: invalid handle");
-        if (bsrh->nd != nd || bsrh->ni != ni || bsrh->dtype != t)
+        // T is the operator's type, or (not for Kronecker operators) the double counterpart of a
+        // single-precision operator: the mixed product of bsr.cpp
+        const bool mixed = !bsrh->is_kron && ((bsrh->dtype == SBX_FLOAT && t == SBX_DOUBLE) ||
+                                              (bsrh->dtype == SBX_CFLOAT && t == SBX_CDOUBLE));
+        if (bsrh->nd != nd || bsrh->ni != ni || (bsrh->dtype != t && !mixed))
             throw Error("Given BSR handle doesn't match the template parameters Nd, Ni, or T");
         if (co != bsrh->co)
             throw Error("Unsupported to use a different coordinate ordering that one used to "

@@ -1635,6 +1635,333 @@ bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) 
     return true;
 }
 
+// Mixed products: an operator kept in single precision (EV: float, float2) applied to vectors of
+// the double counterpart (EX: double, double2).  The values are read in place as EV and widened
+// at the load (exact); products, sums, alpha and the store of y are FP64.  No converted copy of
+// the values exists.
+__device__ __forceinline__ double widen(float a) { return (double)a; }
+__device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
+
+// Generic mixed form: bsr_kernel with separate value and vector types, any block size and
+// pattern; one thread per output element.
+template <typename EV, typename EX, bool YROW, bool XROW>
+__global__ void __launch_bounds__(256) bsr_mixed_kernel(const BsrArgs p) {
+    const int bi = p.bi, bd = p.bd;
+    const long total = p.block_rows * bi * p.ncols;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EX *__restrict__ x = (const EX *)p.x;
+    EX *__restrict__ y = (EX *)p.y;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
+        long i, col;
+        int c;
+        if (YROW) {
+            col = idx % p.ncols;
+            const long t = idx / p.ncols;
+            c = (int)(t % bi);
+            i = t / bi;
+        } else {
+            c = (int)(idx % bi);
+            const long t = idx / bi;
+            i = t % p.block_rows;
+            col = t / p.block_rows;
+        }
+        EX acc = Ops<EX>::zero();
+        const int j0 = p.ii[i], j1 = p.ii[i + 1];
+        for (int j = j0; j < j1; ++j) {
+            const int d0 = p.jj[j];
+            if (d0 < 0) continue;
+            const EV *vb = v + (long)j * bi * bd;
+            for (int e = 0; e < bd; ++e) {
+                const EX a = widen(p.block_im_fast ? vb[c + (long)e * bi] : vb[(long)c * bd + e]);
+                const EX xv = XROW ? x[(long)(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
+                acc = Ops<EX>::fma(a, xv, acc);
+            }
+        }
+        const long img = i * bi + c;
+        EX *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
+        const EX out = Ops<EX>::scale(acc, p.alpha_re, p.alpha_im);
+        *yp = p.add ? Ops<EX>::add(*yp, out) : out;
+    }
+}
+
+template <typename EV, typename EX>
+void launch_mixed_generic(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    const long total = a.block_rows * a.bi * a.ncols;
+    const long blocks = std::min((total + 255) / 256, 65536L);
+    KernelTimer timer("bsr", s);
+    if (yrow && xrow)
+        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, true, true>), dim3(blocks), dim3(256), 0, s, a);
+    else if (yrow && !xrow)
+        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, true, false>), dim3(blocks), dim3(256), 0, s, a);
+    else if (!yrow && xrow)
+        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, false, true>), dim3(blocks), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, false, false>), dim3(blocks), dim3(256), 0, s, a);
+    SBX_HIP_CHECK(hipGetLastError());
+}
+
+// Matrix-core mixed form: bsr_blk_mfma_kernel's structure (one workgroup per block row and
+// group of NT column tiles, a wave per 16-row strip and k-part, U = 4 value loads in flight with
+// the next x block staged behind them, k-parts summed through LDS in wave order) on
+// v_mfma_f64_16x16x4_f64, with the value fragments read in the operator's type:
+//  * lane (row r, k-group kq) reads the VA = 16 / sizeof(EV) consecutive k at (4 ss + kq) VA of
+//    row r as one 16-byte load (2 complex<float>, 4 float) and widens them in registers just
+//    before the MFMAs, so a fragment in flight is 4 VGPRs as in the same-type kernel;
+//  * x is staged in LDS as doubles and B keeps A's k order: lane (column c, kq) takes the same VA
+//    k of column c, 32 bytes, as two 16-byte reads.  LDS banks (ds_read_b128 serves a wave in
+//    four 16-lane groups, each holding every column once with two values of kq; bank (a / 4) mod
+//    64, a 256-byte row of sixteen 16-byte slots): with the 32 bytes adjacent, a read's slot is
+//    2 c (+ 1) mod 16 -- columns c and c + 8 of a lane group on one slot, a 2-way conflict on every
+//    read.  So the two halves of a group lie XW slots apart, image [k-group][half][column]: the
+//    slot of a read is c mod 16, every lane group covers the 16 slots once, no conflict.  (For
+//    either pair that is the same-type kernel's image of the double type.)
+// No LDS-DMA, no atomics; every offset into v, x and y is 64-bit; the 16-byte value load only
+// where all of it lies inside the row (k0 + VA <= bd) of an aligned operator, else by elements.
+template <bool CPLX, int NT>
+__global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p, int yrow, int xrow, int nstrips,
+                                                                 int kparts, int vec_ok) {
+    typedef typename BsrMfmaElem<float, CPLX>::type EV;
+    typedef typename BsrMfmaElem<double, CPLX>::type E;
+    typedef BsrMfma<double>::acc_t acc_t;
+    typedef BlkVec<EV> VV;
+    typedef BlkVec<E> V;
+    constexpr int VA = 16 / (int)sizeof(EV), VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
+    static_assert(VA == 2 * VE, "a group of VA k is two 16-byte pieces of x");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    E *xs = (E *)smem;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const E *__restrict__ x = (const E *)p.x;
+    E *__restrict__ y = (E *)p.y;
+    const int bi = p.bi, bd = p.bd;
+    const int nss = (bd + 4 * VA - 1) / (4 * VA), kpad = nss * 4 * VA; // k-steps of 4 VA
+    const int xbuf = kpad * XW;                                        // elements per x buffer
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long i = blockIdx.x, col0 = (long)blockIdx.y * XW;
+    const bool active = w < nstrips * kparts;
+    const int strip = w % nstrips, kp = w / nstrips;
+    const int ar = lane & 15, kq = lane >> 4;
+    const int arow = strip * 16 + ar;
+    const bool arow_ok = active && arow < bi;
+
+    // staging as in bsr_blk_mfma_kernel: element e = outer * nin + inner, inner the fastest
+    // index of x, walked by steps of the workgroup size; image [k / VE][column][k % VE]
+    const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
+    const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
+    auto stage = [&](int j, int buf) {
+        const int dj = p.jj[j];
+        if (dj < 0) return;
+        E *dst = xs + buf * xbuf;
+        int in = in0, out = out0;
+        while (out < nout) {
+            E t[4];
+            int kk[4], cc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                kk[q] = xrow ? out : in;
+                cc[q] = xrow ? in : out;
+                const long col = col0 + cc[q];
+                t[q] = E{};
+                if (out < nout && kk[q] < bd && col < p.ncols)
+                    t[q] = xrow ? x[(long)(dj + kk[q]) * p.ldx + col] : x[(long)(dj + kk[q]) + col * p.ldx];
+                if (out >= nout) kk[q] = -1;
+                in += din;
+                out += dout;
+                if (in >= nin) {
+                    in -= nin;
+                    ++out;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
+        }
+    };
+    auto load_a = [&](const EV *vb, int ss) {
+        VV a;
+#pragma unroll
+        for (int t = 0; t < VA; ++t) a.e[t] = EV{};
+        const int k0 = (ss * 4 + kq) * VA;
+        if (arow_ok && k0 < bd) {
+            if (!p.block_im_fast) {
+                const EV *src = vb + (long)arow * bd + k0;
+                if (vec_ok && k0 + VA <= bd) {
+                    a = *(const VV *)src;
+                } else {
+#pragma unroll
+                    for (int t = 0; t < VA; ++t)
+                        if (k0 + t < bd) a.e[t] = src[t];
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < VA; ++t)
+                    if (k0 + t < bd) a.e[t] = vb[arow + (long)(k0 + t) * bi];
+            }
+        }
+        return a;
+    };
+    acc_t accR[NT], accI[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
+    auto apply = [&](const VV &af, int ss, const E *xb) {
+        E a[VA]; // the up-conversion: exact
+#pragma unroll
+        for (int t = 0; t < VA; ++t) a[t] = widen(af.e[t]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const V b = *(const V *)(xb + (((ss * 4 + kq) * 2 + h) * XW + nt * 16 + ar) * VE);
+#pragma unroll
+                for (int u = 0; u < VE; ++u) {
+                    const E ak = a[h * VE + u];
+                    if constexpr (CPLX) {
+                        accR[nt] = BsrMfma<double>::mma(ak.x, b.e[u].x, accR[nt]);
+                        accI[nt] = BsrMfma<double>::mma(ak.x, b.e[u].y, accI[nt]);
+                        accR[nt] = BsrMfma<double>::mma(-ak.y, b.e[u].y, accR[nt]);
+                        accI[nt] = BsrMfma<double>::mma(ak.y, b.e[u].x, accI[nt]);
+                    } else {
+                        accR[nt] = BsrMfma<double>::mma(ak, b.e[u], accR[nt]);
+                    }
+                }
+            }
+        }
+    };
+
+    const int jb = p.ii[i], je = p.ii[i + 1];
+    if (jb < je) stage(jb, 0);
+    __syncthreads();
+    for (int j = jb; j < je; ++j) {
+        const int buf = (j - jb) & 1;
+        const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
+        const EV *vb = v + (long)j * bi * bd;
+        const E *xb = xs + buf * xbuf;
+        // the block's first U fragments are in flight while the next x block is staged
+        VV a[U];
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) a[u] = load_a(vb, kp + u * kparts);
+        }
+        if (j + 1 < je) stage(j + 1, buf ^ 1);
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (kp + u * kparts < nss) apply(a[u], kp + u * kparts, xb);
+            for (int ss = kp + U * kparts; ss < nss; ss += U * kparts) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) a[u] = load_a(vb, ss + u * kparts);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (ss + u * kparts < nss) apply(a[u], ss + u * kparts, xb);
+            }
+        }
+        __syncthreads(); // buffer buf is free again, buffer buf ^ 1 is complete
+    }
+    if (kparts > 1) {
+        // the x buffers are dead (every path above ends in a barrier): partial tiles of the
+        // k-parts 1.. to LDS, summed by part 0 in part order
+        double *red = (double *)smem;
+        if (active && kp > 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    red[(((w * NT + nt) * NC + 0) * 4 + q) * 64 + lane] = accR[nt][q];
+                    if constexpr (CPLX) red[(((w * NT + nt) * NC + 1) * 4 + q) * 64 + lane] = accI[nt][q];
+                }
+        }
+        __syncthreads();
+        if (active && kp == 0) {
+            for (int k2 = 1; k2 < kparts; ++k2) {
+                const int w2 = strip + k2 * nstrips;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        accR[nt][q] += red[(((w2 * NT + nt) * NC + 0) * 4 + q) * 64 + lane];
+                        if constexpr (CPLX) accI[nt][q] += red[(((w2 * NT + nt) * NC + 1) * 4 + q) * 64 + lane];
+                    }
+            }
+        }
+    }
+    if (!active || kp != 0) return;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = strip * 16 + BsrMfma<double>::row(lane, q);
+            const long col = col0 + nt * 16 + ar;
+            if (row >= bi || col >= p.ncols) continue;
+            const long img = i * bi + row;
+            E *yp = yrow ? y + img * p.ldy + col : y + img + col * p.ldy;
+            E out;
+            if constexpr (CPLX)
+                out = Ops<E>::scale(E{accR[nt][q], accI[nt][q]}, p.alpha_re, p.alpha_im);
+            else
+                out = Ops<E>::scale(accR[nt][q], p.alpha_re, p.alpha_im);
+            *yp = p.add ? Ops<E>::add(*yp, out) : out;
+        }
+}
+
+/// false: not this shape (the generic mixed kernel runs).  Limits as launch_bsr_blk_mfma, by the
+/// vector type: bi <= 128, two x buffers of kpad x 16 NT doubles within 64 KB of LDS (kpad: bd
+/// rounded up to 4 VA; bd <= 128 for complex<double> and 256 for double vectors), NT reduced to
+/// stay within 32 KB where possible, at most 65535 groups of NT column tiles.
+template <bool CPLX>
+bool launch_bsr_blk_mfma_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    typedef typename BsrMfmaElem<float, CPLX>::type EV;
+    typedef typename BsrMfmaElem<double, CPLX>::type E;
+    constexpr int ES = (int)sizeof(E), VA = 16 / (int)sizeof(EV);
+    const int nstrips = (a.bi + 15) / 16;
+    if (nstrips > 8 || a.block_rows >= (1L << 31)) return false;
+    const int nss = (a.bd + 4 * VA - 1) / (4 * VA), kpad = nss * 4 * VA;
+    const int kparts = std::min(nstrips == 1 ? 4 : nstrips == 2 ? 2 : 1, nss);
+    const int nw = nstrips * kparts;
+    auto lds_of = [&](int nt) {
+        const long xb = 2L * kpad * nt * 16 * ES;
+        const long red = kparts > 1 ? (long)nw * nt * (CPLX ? 2 : 1) * 4 * 64 * (long)sizeof(double) : 0;
+        return std::max(xb, red);
+    };
+    int nt = a.ncols <= 16 ? 1 : a.ncols <= 32 ? 2 : 4;
+    while (nt > 1 && lds_of(nt) > 32768) nt /= 2;
+    const long lds = lds_of(nt);
+    if (lds > 65536) return false;
+    const long ngroups = (a.ncols + nt * 16 - 1) / (nt * 16);
+    if (ngroups > 65535) return false;
+    const int vec_ok = ((long)a.bd * (long)sizeof(EV)) % 16 == 0 && ((size_t)a.v & 15) == 0 ? 1 : 0;
+    g_bsr_tune.last = 16;
+    KernelTimer timer("bsr", s);
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
+                           yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
+    };
+    if (nt == 1) go(bsr_blk_mfma_mixed_kernel<CPLX, 1>);
+    else if (nt == 2) go(bsr_blk_mfma_mixed_kernel<CPLX, 2>);
+    else go(bsr_blk_mfma_mixed_kernel<CPLX, 4>);
+    SBX_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+/// A mixed product (values EV, vectors EX).  The matrix-core form takes dense blocks from
+/// blk_min x blk_min on (blk_mfma, blk_min and variant as for bsr_blk_mfma_kernel) where it was
+/// measured faster than the generic mixed form by more than the larger round-to-round spread of
+/// the two (8^4 9-point operators, complex<float> values, complex<double> vectors,
+/// profiles/bsr_mixed_measure.txt): 32x32 blocks and larger at any column count (1.25-5.8x), 16x16
+/// and 24x24 from 4 columns (1.04x / 1.02x at 4, 2.6-4.0x from 12; at one column 0.73x / 0.89x);
+/// between the measured sizes the bound goes by the block's elements: 1024 and more at any column
+/// count, fewer from 4 columns (float -> double: the same bound, not measured).  blk_mfma 2: no
+/// column bound.  3x3 and 12x12 blocks and everything else run the generic mixed form.
+template <typename EV, typename EX>
+void launch_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    constexpr bool CPLX = std::is_same<EX, double2>::value;
+    if (g_bsr_tune.mixed && g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
+        a.bd >= g_bsr_tune.blk_min &&
+        a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : 4) &&
+        launch_bsr_blk_mfma_mixed<CPLX>(a, yrow, xrow, s))
+        return;
+    launch_mixed_generic<EV, EX>(a, yrow, xrow, s);
+}
+
 template <typename E> bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
     if constexpr (std::is_same<E, double2>::value) return launch_bsr_blk_mfma<double, true>(a, yrow, xrow, s);
     else if constexpr (std::is_same<E, double>::value) return launch_bsr_blk_mfma<double, false>(a, yrow, xrow, s);
@@ -1747,6 +2074,14 @@ void launch_bsr(const BsrDesc &d, int device) {
     a.nt = g_bsr_tune.nt;
     a.tiles[0] = d.tiles[0];
     a.tiles[1] = d.tiles[1];
+    if (d.tv != d.t) {
+        // single-precision values, double-precision vectors (bsr_krylov admits these two pairs)
+        if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE)
+            return launch_mixed<float2, double2>(a, d.y_row_major, d.x_row_major, s);
+        if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE)
+            return launch_mixed<float, double>(a, d.y_row_major, d.x_row_major, s);
+        throw Error("bsr: unsupported pair of value and vector types");
+    }
     switch (d.t) {
     case SBX_CDOUBLE: return launch_typed<double2>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);
     case SBX_CFLOAT: return launch_typed<float2>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);

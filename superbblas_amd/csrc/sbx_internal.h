@@ -333,6 +333,13 @@ struct BsrTune {
                       ///< was measured faster: blocks of 1024 elements and more at any column count, of
                       ///< 576 and more from 4 rhs columns, smaller ones from 12; 2 = at any column count)
     int blk_min = 16; ///< ... block image and domain sizes from this on (4..: lower for comparison runs)
+    int mixed = 1; ///< single-precision operators applied to vectors of the double counterpart (float ->
+                   ///< double, complex<float> -> complex<double>; the values are read in place and
+                   ///< converted at the load, never copied): 1 = the blocks that blk_mfma / blk_min
+                   ///< admit go to bsr_blk_mfma_mixed_kernel where it was measured faster (blocks of
+                   ///< 1024 elements and more at any column count, smaller ones from 4 rhs columns;
+                   ///< blk_mfma 2: at any column count), 0 = every mixed product on the generic
+                   ///< mixed kernel
     /// read-back ("bsr.last_kernel"; atomic: launches may come from several host threads): the form
     /// of the last launch -- 1 one thread per block (3x3), 2 split rows (3x3), 3 row chunks (3x3),
     /// 4 site tiles (3x3),
@@ -341,9 +348,14 @@ struct BsrTune {
     /// per row), 11 12x12 generic rows, 12 Kronecker spin first with XOR-partner spin rows,
     /// 13 site tiles of 8 sites and 16 columns (3x3), 14 dense blocks of blk_min and more on MFMA
     /// (bsr_blk_mfma_kernel), 15 Kronecker adjoint, a thread per (domain site, column)
-    /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element,
+    /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element -- or, with
+    /// last_mixed 1 (Kronecker operators are never mixed), dense blocks with single-precision
+    /// values and double-precision vectors on MFMA (bsr_blk_mfma_mixed_kernel),
     /// 0 another kernel
     std::atomic<int> last{0};
+    /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type
+    /// than its vectors, else 0
+    std::atomic<int> last_mixed{0};
 };
 extern BsrTune g_bsr_tune;
 /// dense solvers: matrices up to 16 x 16 packed 64 / n per wave -- 1: Cholesky and LU
@@ -393,7 +405,8 @@ struct TileSched {
 };
 
 struct BsrDesc {
-    int t;
+    int t;           ///< type of x and y
+    int tv;          ///< type of the values: t, or its single-precision counterpart (mixed product)
     long block_rows; ///< number of block rows
     int bi, bd;      ///< block image / domain sizes
     const int *ii;   ///< CSR row pointer (block_rows+1), device
