@@ -613,6 +613,14 @@ void contraction(T alpha, const PartitionItem<Nd0> *p0, const Coor<Nd0> &from0,
 /// the caller's array, no converted copy is kept -- and products, sums, alpha, beta and y are
 /// double: the result is the product of the up-converted operator with x.  Every other pair of
 /// types, and any type difference on an operator of create_kron_bsr, throws as before.
+///
+/// The image side (x with the image labels, y = alpha A^H x) of a create_bsr operator: by default
+/// the first such product makes a conjugated, regrouped copy of the value blocks that all later
+/// A^H products read -- a snapshot (values changed in place afterwards show in A x, not in A^H x)
+/// and as many device bytes again as the values.  sbx_tune_set("bsr.adj_inplace", 1) makes A^H
+/// products read the caller's value array in place, as A does: no copy, and A^H follows the
+/// changes (3x3 and 12x12 operators then give up their LDS-DMA kernels
+/// on that side).  Operators of create_kron_bsr are always in place.
 template <std::size_t Nd, std::size_t Ni, typename T>
 void create_bsr(const PartitionItem<Ni> *pim, const Coor<Ni> &dimi, const PartitionItem<Nd> *pdm,
                 const Coor<Nd> &dimd, int ncomponents, const Coor<Ni> &blockim,

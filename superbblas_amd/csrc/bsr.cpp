@@ -15,6 +15,8 @@
 //    them (bsr.h:1914-1928), and the local product runs kernels_bsr_kron.hip.
 //  * contracting with the image side (x has the image labels) applies A^H: a conj-transposed
 //    operator built on first use (make_transposed), whose overlapping image pieces are summed.
+//    For plain operators its values are a conjugated, regrouped copy made at the first such
+//    product, or -- bsr.adj_inplace -- A's own array read through an entry list (adjoint_values).
 //    For Kronecker operators A^H copies no values: per domain site of A it lists A's nonzeros
 //    pointing at the site, and the kernel reads A's own blocks and spin matrices conj-transposed
 //    (bsr_kron_adj_kernel; the reference's local Kronecker operators throw "unsupported
@@ -55,6 +57,14 @@ struct BsrComp {
     // adj_ptr [block_rows + 1] the row pointer over A's domain sites, adj_ent A's nonzero index
     // k = I * nnz + mu of each entry, ascending within a site (nnz_per_row holds A's nnz)
     int *adj_ptr = nullptr, *adj_ent = nullptr;
+    // the adjoint of a plain operator A (make_transposed): ii / jj are the transposed pattern; the
+    // values come from one of two sources, each built at the first product that asks for it
+    // (adjoint_values): the copy (owned_v = v: A's blocks conjugated and regrouped by block
+    // column, bsr.adj_inplace 0) or A's own array adj_src_v read through adj_ent, A's nonzero
+    // index per entry (bsr.adj_inplace 1).  adj_perm is the host list both are made from
+    const void *adj_src_v = nullptr;
+    std::vector<int> adj_perm;
+    long long adj_copy_bytes = 0; // of owned_v, as counted in bsr.adj_copy_bytes
 };
 
 struct BsrOp {
@@ -78,6 +88,7 @@ struct BsrOp {
             if (c.ii) (void)hipFree(c.ii);
             if (c.jj) (void)hipFree(c.jj);
             if (c.owned_v) (void)hipFree(c.owned_v);
+            if (c.adj_copy_bytes) g_bsr_tune.adj_copy_bytes -= c.adj_copy_bytes;
             if (c.owned_kron) (void)hipFree(c.owned_kron);
             for (void *b : c.tile_buf)
                 if (b) (void)hipFree(b);
@@ -476,7 +487,8 @@ namespace {
 /// The conjugate transpose A^H of an operator, for contractions with the image side of A (the
 /// reference's transSp: hipsparse bsrmm with CONJUGATE_TRANSPOSE, bsr.h:1001-1029, 1942): image
 /// partition = A's domain partition (which may overlap across components: the halos), domain
-/// partition = A's image partition, blocks conj-transposed and regrouped by block column.
+/// partition = A's image partition, blocks conj-transposed and regrouped by block column (the
+/// pattern here; the values by adjoint_values, copied or read from A's array in place).
 /// Kronecker operators: a domain site of A is referenced by any number of nonzeros (halo sites
 /// by fewer; on a lattice of extent 2 both neighbours of a direction are one site), and the spin
 /// matrix of a nonzero goes with its slot mu in A's row -- so A^H is a row pointer over A's
@@ -515,7 +527,6 @@ BsrOp *make_transposed(const BsrOp &a) {
                 break;
             }
     const long bi = volume(a.blocki), bd = volume(a.blockd);
-    const std::size_t es = dtype_size(a.dtype);
     const long kd = volume(a.krond);
     for (int c = 0; a.is_kron && c < (int)a.comps.size(); ++c) {
         const BsrComp &ac = a.comps[c];
@@ -586,18 +597,54 @@ BsrOp *make_transposed(const BsrOp &a) {
         SBX_HIP_CHECK(hipMalloc(&bc.jj, sizeof(int) * std::max(nnz, 1)));
         SBX_HIP_CHECK(hipMemcpy(bc.ii, cnt.data(), sizeof(int) * (ncb + 1), hipMemcpyHostToDevice));
         SBX_HIP_CHECK(hipMemcpy(bc.jj, tjj.data(), sizeof(int) * std::max(nnz, 1), hipMemcpyHostToDevice));
-        // values: block perm[q] of A, conjugated, at position q
-        SBX_HIP_CHECK(hipMalloc(&bc.owned_v, es * bi * bd * std::max(nnz, 1)));
-        Scratch dperm(sizeof(int) * std::max(nnz, 1), bc.dev);
-        SBX_HIP_CHECK(hipMemcpyAsync(dperm.ptr, perm.data(), sizeof(int) * std::max(nnz, 1),
-                                     hipMemcpyHostToDevice, get_stream(bc.dev)));
-        launch_gather_blocks(a.dtype, ac.v, (const int *)dperm.ptr, nnz, bi * bd, true,
-                             bc.owned_v, bc.dev);
-        SBX_HIP_CHECK(hipStreamSynchronize(get_stream(bc.dev)));
-        bc.v = bc.owned_v;
+        // values: block perm[q] of A, conjugated, at position q -- copied or read in place, by
+        // the products' choice (adjoint_values)
+        perm.resize(nnz);
+        bc.adj_perm = std::move(perm);
+        bc.adj_src_v = ac.v;
         t->comps.push_back(std::move(bc));
     }
     return t.release();
+}
+
+/// The value source of t = A^H (a plain operator's, make_transposed) that a product is about to
+/// read, built on first use; the caller holds the mutex that guards A's `transposed`.  The copy:
+/// block adj_perm[q] of A conjugated at position q (a snapshot of A's values at this moment).
+/// In place: the entry list on the device, 4 bytes per nonzero block; the kernels read A's own
+/// array through it, so nothing of A's values is kept.  The two are independent: one operator
+/// serves both settings of bsr.adj_inplace in either order, and one only ever used in place
+/// never allocates the copy.
+void adjoint_values(const BsrOp &a, BsrOp &t, bool inplace) {
+    const long be = volume(a.blocki) * volume(a.blockd);
+    const std::size_t es = dtype_size(a.dtype);
+    for (BsrComp &bc : t.comps) {
+        if (bc.block_rows == 0 || (inplace ? bc.adj_ent != nullptr : bc.owned_v != nullptr)) continue;
+        const long nnz = (long)bc.adj_perm.size();
+        const std::size_t ibytes = sizeof(int) * std::max(nnz, 1L);
+        set_device(bc.dev);
+        if (inplace) {
+            int *ent = nullptr;
+            SBX_HIP_CHECK(hipMalloc(&ent, ibytes));
+            if (nnz > 0 && hipMemcpy(ent, bc.adj_perm.data(), sizeof(int) * nnz,
+                                     hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(ent);
+                throw Error("bsr: copying the adjoint's entry list failed");
+            }
+            bc.adj_ent = ent;
+            continue;
+        }
+        SBX_HIP_CHECK(hipMalloc(&bc.owned_v, es * be * std::max(nnz, 1L)));
+        bc.adj_copy_bytes = (long long)(es * be * nnz);
+        g_bsr_tune.adj_copy_bytes += bc.adj_copy_bytes;
+        bc.v = bc.owned_v;
+        Scratch dperm(ibytes, bc.dev);
+        if (nnz > 0)
+            SBX_HIP_CHECK(hipMemcpyAsync(dperm.ptr, bc.adj_perm.data(), sizeof(int) * nnz,
+                                         hipMemcpyHostToDevice, get_stream(bc.dev)));
+        launch_gather_blocks(a.dtype, bc.adj_src_v, (const int *)dperm.ptr, nnz, be, true,
+                             bc.owned_v, bc.dev);
+        SBX_HIP_CHECK(hipStreamSynchronize(get_stream(bc.dev)));
+    }
 }
 
 } // namespace
@@ -644,13 +691,13 @@ Layout dense_layout(const std::string &spatial, const std::string &cl, const std
     return Layout{false, false, 0};
 }
 
-} // namespace
-
-void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
-                const std::string &od, const DistTensor &x_in, const Coor &fromx,
-                const Coor &sizex, const Scalar &beta, const DistTensor &y_in, const Coor &fromy,
-                const Coor &sizey, char okr, const Comm &comm_in, bool just_local,
-                std::function<void()> *deferred) {
+/// bsr_krylov; adj_inplace: `op` is the transposed operator of a plain operator and this product
+/// reads the values in place (bsr.adj_inplace as read by the caller's product)
+void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const std::string &od,
+            const DistTensor &x_in, const Coor &fromx, const Coor &sizex, const Scalar &beta,
+            const DistTensor &y_in, const Coor &fromy, const Coor &sizey, char okr,
+            const Comm &comm_in, bool just_local, std::function<void()> *deferred,
+            bool adj_inplace) {
     if (deferred) *deferred = nullptr;
     if ((int)oi.size() != op.ni || (int)od.size() != op.nd)
         throw Error("bsr_krylov: labels don't match the operator");
@@ -697,13 +744,16 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
         throw Error("Unsupported to contract dense input tensor with domain and image dimensions "
                     "of the sparse tensor");
     if (x_image) {
+        // (the key is read once per product: the value source built here is the one launched)
+        const bool inplace = !op.is_kron && g_bsr_tune.adj_inplace != 0;
         {
             static std::mutex mu; // (one host thread builds it)
             std::lock_guard<std::mutex> lock(mu);
             if (!op.transposed) op.transposed.reset(make_transposed(op));
+            if (!op.is_kron) adjoint_values(op, *op.transposed, inplace);
         }
-        return bsr_krylov(*op.transposed, alpha, od, oi, x_in, fromx, sizex, beta, y_in, fromy,
-                          sizey, okr, comm_in, just_local, deferred);
+        return krylov(*op.transposed, alpha, od, oi, x_in, fromx, sizex, beta, y_in, fromy, sizey,
+                      okr, comm_in, just_local, deferred, inplace);
     }
     // Label classes (bsr.h:1722-1795): x has domain labels + C (+ okr); y image labels + C (+okr)
     std::string C;
@@ -989,6 +1039,11 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
                     d.adj_ent = bc.adj_ent;
                     launch_bsr_kron(d, bc.dev);
                 } else {
+                    if (adj_inplace) {
+                        // A^H on A's own values (for a host component the device mirror A uses)
+                        d.v = bc.adj_src_v;
+                        d.adj_ent = bc.adj_ent;
+                    }
                     launch_bsr(d, bc.dev);
                 }
             }
@@ -1019,6 +1074,17 @@ void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
         *deferred = product;
     else
         product();
+}
+
+} // namespace
+
+void bsr_krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi,
+                const std::string &od, const DistTensor &x_in, const Coor &fromx,
+                const Coor &sizex, const Scalar &beta, const DistTensor &y_in, const Coor &fromy,
+                const Coor &sizey, char okr, const Comm &comm_in, bool just_local,
+                std::function<void()> *deferred) {
+    krylov(op, alpha, oi, od, x_in, fromx, sizex, beta, y_in, fromy, sizey, okr, comm_in,
+           just_local, deferred, false);
 }
 
 } // namespace sbx

@@ -456,6 +456,8 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "bsr.blk_mfma") g_bsr_tune.blk_mfma = (int)value;
         else if (k == "bsr.blk_min") g_bsr_tune.blk_min = (int)value;
         else if (k == "bsr.mixed") g_bsr_tune.mixed = (int)value;
+        else if (k == "bsr.adj_inplace") g_bsr_tune.adj_inplace = (int)value;
+        else if (k == "bsr.adj_copy_bytes") throw Error("tune_set: bsr.adj_copy_bytes is read-only");
         else if (k == "bsr.tile") g_bsr_tune.tile = (int)value;
         else if (k == "bsr.tile_min_cols") g_bsr_tune.tile_min_cols = value;
         else if (k == "gemm.m3") g_gemm_tune.m3 = (int)value;
@@ -537,6 +539,8 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "bsr.mixed") *value = g_bsr_tune.mixed;
         else if (k == "bsr.last_kernel") *value = g_bsr_tune.last;
         else if (k == "bsr.last_mixed") *value = g_bsr_tune.last_mixed;
+        else if (k == "bsr.adj_inplace") *value = g_bsr_tune.adj_inplace;
+        else if (k == "bsr.adj_copy_bytes") *value = g_bsr_tune.adj_copy_bytes;
         else if (k == "gemm.m3") *value = g_gemm_tune.m3;
         else if (k == "gemm.splits") *value = g_gemm_tune.splits;
         else if (k == "gemm.t48") *value = g_gemm_tune.t48;

@@ -1596,11 +1596,202 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_kernel(const BsrArgs p, int 
         }
 }
 
+// The in-place adjoint on the matrix cores (bsr.adj_inplace): bsr_blk_mfma_kernel, line by line,
+// on the transposed operator's pattern over A's own value array.  Entry j of a block row reads
+// block ent[j] of A instead of block j of the copy, and the imaginary parts are negated in
+// registers as a fragment is loaded (real types load unchanged; the zeros of the padding are
+// never loaded and stay as they are): the bytes read per block are the copy's, plus the 4 of
+// ent[j].  The block is A's storage read in the flipped order (p.block_im_fast is the opposite of
+// A's), so A's row-major blocks are the image-fastest case here, exactly as on the copy, and the
+// 16-byte loads apply where they would on the copy and A's array is 16-byte aligned.  Entries are
+// in ascending nonzero index of A within a block column, the copy's order; the conjugation is an
+// exact sign flip and every other operation is the same, so the result has the bits of
+// bsr_blk_mfma_kernel on the copy.  No LDS-DMA, no atomics; every offset into v, x and y is 64-bit.
+template <typename R, bool CPLX, int NT>
+__global__ void __launch_bounds__(512) bsr_blk_mfma_adj_kernel(const BsrArgs p, const int *__restrict__ ent,
+                                                               int yrow, int xrow, int nstrips, int kparts,
+                                                               int vec_ok) {
+    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    typedef typename BsrMfma<R>::acc_t acc_t;
+    typedef BlkVec<E> V;
+    constexpr int VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    E *xs = (E *)smem;
+    const E *__restrict__ v = (const E *)p.v;
+    const E *__restrict__ x = (const E *)p.x;
+    E *__restrict__ y = (E *)p.y;
+    const int bi = p.bi, bd = p.bd;
+    const int nss = (bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE; // k-steps of 4 VE
+    const int xbuf = kpad * XW;                                        // elements per x buffer
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long i = blockIdx.x, col0 = (long)blockIdx.y * XW;
+    const bool active = w < nstrips * kparts;
+    const int strip = w % nstrips, kp = w / nstrips;
+    const int ar = lane & 15, kq = lane >> 4;
+    const int arow = strip * 16 + ar;
+    const bool arow_ok = active && arow < bi;
+
+    // staging order: element e = outer * nin + inner, inner the fastest index of x (the rhs
+    // column for row-major x, else the domain row), walked by steps of the workgroup size
+    const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
+    const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
+    auto stage = [&](int j, int buf) {
+        const int dj = p.jj[j];
+        if (dj < 0) return;
+        E *dst = xs + buf * xbuf;
+        int in = in0, out = out0;
+        while (out < nout) {
+            E t[4];
+            int kk[4], cc[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                kk[q] = xrow ? out : in;
+                cc[q] = xrow ? in : out;
+                const long col = col0 + cc[q];
+                t[q] = E{};
+                if (out < nout && kk[q] < bd && col < p.ncols)
+                    t[q] = xrow ? x[(long)(dj + kk[q]) * p.ldx + col] : x[(long)(dj + kk[q]) + col * p.ldx];
+                if (out >= nout) kk[q] = -1;
+                in += din;
+                out += dout;
+                if (in >= nin) {
+                    in -= nin;
+                    ++out;
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
+        }
+    };
+    auto load_a = [&](const E *vb, int ss) {
+        V a;
+#pragma unroll
+        for (int t = 0; t < VE; ++t) a.e[t] = E{};
+        const int k0 = (ss * 4 + kq) * VE;
+        if (arow_ok && k0 < bd) {
+            if (!p.block_im_fast) {
+                const E *src = vb + (long)arow * bd + k0;
+                if (vec_ok && k0 + VE <= bd) {
+                    a = *(const V *)src;
+#pragma unroll
+                    for (int t = 0; t < VE; ++t) a.e[t] = Ops<E>::conj(a.e[t]);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < VE; ++t)
+                        if (k0 + t < bd) a.e[t] = Ops<E>::conj(src[t]);
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < VE; ++t)
+                    if (k0 + t < bd) a.e[t] = Ops<E>::conj(vb[arow + (long)(k0 + t) * bi]);
+            }
+        }
+        return a;
+    };
+    acc_t accR[NT], accI[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
+    auto apply = [&](const V &a, int ss, const E *xb) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const V b = *(const V *)(xb + ((ss * 4 + kq) * XW + nt * 16 + ar) * VE);
+#pragma unroll
+            for (int t = 0; t < VE; ++t) {
+                if constexpr (CPLX) {
+                    accR[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].x, accR[nt]);
+                    accI[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].y, accI[nt]);
+                    accR[nt] = BsrMfma<R>::mma(-a.e[t].y, b.e[t].y, accR[nt]);
+                    accI[nt] = BsrMfma<R>::mma(a.e[t].y, b.e[t].x, accI[nt]);
+                } else {
+                    accR[nt] = BsrMfma<R>::mma(a.e[t], b.e[t], accR[nt]);
+                }
+            }
+        }
+    };
+
+    const int jb = p.ii[i], je = p.ii[i + 1];
+    if (jb < je) stage(jb, 0);
+    __syncthreads();
+    for (int j = jb; j < je; ++j) {
+        const int buf = (j - jb) & 1;
+        const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
+        const E *vb = v + (long)ent[j] * bi * bd; // (wave-uniform)
+        const E *xb = xs + buf * xbuf;
+        // the block's first U fragments are in flight while the next x block is staged
+        V a[U];
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) a[u] = load_a(vb, kp + u * kparts);
+        }
+        if (j + 1 < je) stage(j + 1, buf ^ 1);
+        if (on) {
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (kp + u * kparts < nss) apply(a[u], kp + u * kparts, xb);
+            for (int ss = kp + U * kparts; ss < nss; ss += U * kparts) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) a[u] = load_a(vb, ss + u * kparts);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (ss + u * kparts < nss) apply(a[u], ss + u * kparts, xb);
+            }
+        }
+        __syncthreads(); // buffer buf is free again, buffer buf ^ 1 is complete
+    }
+    if (kparts > 1) {
+        // the x buffers are dead (every path above ends in a barrier): partial tiles of the
+        // k-parts 1.. to LDS, summed by part 0 in part order
+        R *red = (R *)smem;
+        if (active && kp > 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    red[(((w * NT + nt) * NC + 0) * 4 + q) * 64 + lane] = accR[nt][q];
+                    if constexpr (CPLX) red[(((w * NT + nt) * NC + 1) * 4 + q) * 64 + lane] = accI[nt][q];
+                }
+        }
+        __syncthreads();
+        if (active && kp == 0) {
+            for (int k2 = 1; k2 < kparts; ++k2) {
+                const int w2 = strip + k2 * nstrips;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        accR[nt][q] += red[(((w2 * NT + nt) * NC + 0) * 4 + q) * 64 + lane];
+                        if constexpr (CPLX) accI[nt][q] += red[(((w2 * NT + nt) * NC + 1) * 4 + q) * 64 + lane];
+                    }
+            }
+        }
+    }
+    if (!active || kp != 0) return;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int row = strip * 16 + BsrMfma<R>::row(lane, q);
+            const long col = col0 + nt * 16 + ar;
+            if (row >= bi || col >= p.ncols) continue;
+            const long img = i * bi + row;
+            E *yp = yrow ? y + img * p.ldy + col : y + img + col * p.ldy;
+            E out;
+            if constexpr (CPLX)
+                out = Ops<E>::scale(E{accR[nt][q], accI[nt][q]}, p.alpha_re, p.alpha_im);
+            else
+                out = Ops<E>::scale(accR[nt][q], p.alpha_re, p.alpha_im);
+            *yp = p.add ? Ops<E>::add(*yp, out) : out;
+        }
+}
+
 /// false: not this shape (the generic kernel runs).  Limits: bi <= 128 (8 strips, one wave each),
 /// two x buffers of 16 columns within 64 KB of LDS (bd <= 128 for complex<double>, 256 for
 /// 8-byte and 512 for 4-byte elements), at most 65535 groups of NT column tiles.
+/// ent: the in-place adjoint (bsr_blk_mfma_adj_kernel), under the same limits.
 template <typename R, bool CPLX>
-bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
     typedef typename BsrMfmaElem<R, CPLX>::type E;
     constexpr int ES = (int)sizeof(E), VE = 16 / ES;
     const int nstrips = (a.bi + 15) / 16;
@@ -1622,8 +1813,19 @@ bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) 
     const long ngroups = (a.ncols + nt * 16 - 1) / (nt * 16);
     if (ngroups > 65535) return false;
     const int vec_ok = ((long)a.bd * ES) % 16 == 0 && ((size_t)a.v & 15) == 0 ? 1 : 0;
-    g_bsr_tune.last = 14;
+    g_bsr_tune.last = ent ? 17 : 14;
     KernelTimer timer("bsr", s);
+    auto go_adj = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
+                           ent, yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
+    };
+    if (ent) {
+        if (nt == 1) go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 1>);
+        else if (nt == 2) go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 2>);
+        else go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 4>);
+        SBX_HIP_CHECK(hipGetLastError());
+        return true;
+    }
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
                            yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
@@ -1962,11 +2164,20 @@ void launch_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
     launch_mixed_generic<EV, EX>(a, yrow, xrow, s);
 }
 
-template <typename E> bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
-    if constexpr (std::is_same<E, double2>::value) return launch_bsr_blk_mfma<double, true>(a, yrow, xrow, s);
-    else if constexpr (std::is_same<E, double>::value) return launch_bsr_blk_mfma<double, false>(a, yrow, xrow, s);
-    else if constexpr (std::is_same<E, float2>::value) return launch_bsr_blk_mfma<float, true>(a, yrow, xrow, s);
-    else return launch_bsr_blk_mfma<float, false>(a, yrow, xrow, s);
+template <typename E>
+bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
+    if constexpr (std::is_same<E, double2>::value) return launch_bsr_blk_mfma<double, true>(a, yrow, xrow, s, ent);
+    else if constexpr (std::is_same<E, double>::value) return launch_bsr_blk_mfma<double, false>(a, yrow, xrow, s, ent);
+    else if constexpr (std::is_same<E, float2>::value) return launch_bsr_blk_mfma<float, true>(a, yrow, xrow, s, ent);
+    else return launch_bsr_blk_mfma<float, false>(a, yrow, xrow, s, ent);
+}
+
+/// Whether launch_typed's dense-block clause takes these blocks at this column count
+/// (bsr.blk_mfma, bsr.blk_min, bsr.variant and the measured column thresholds, see launch_typed)
+inline bool blk_mfma_admits(const BsrArgs &a) {
+    return g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
+           a.bd >= g_bsr_tune.blk_min &&
+           a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : a.bi * a.bd >= 24 * 24 ? 4 : 12);
 }
 
 template <typename E>
@@ -1997,13 +2208,88 @@ void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipSt
     // larger at any column count (1.15-8.7x), 24x24 from 4 columns (complex<double> n = 1: a
     // tie), 16x16 from 12 columns (complex<double> n = 1 / 4: 0.75x / 0.93x); between the
     // measured sizes the bound goes by the block's elements.  blk_mfma 2: no column bound
-    else if (g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
-             a.bd >= g_bsr_tune.blk_min &&
-             a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : a.bi * a.bd >= 24 * 24 ? 4 : 12) &&
-             launch_blk<E>(a, yrow, xrow, s))
+    else if (blk_mfma_admits(a) && launch_blk<E>(a, yrow, xrow, s))
         return;
     else
         launch_layouts<E, 0, 0>(a, yrow, xrow, blocks, s);
+}
+
+// The in-place adjoint, generic form (bsr.adj_inplace): bsr_kernel / bsr_mixed_kernel on the
+// transposed pattern with an entry indirection.  One thread per output element (block column J
+// of A, component c, rhs column); entry j of J reads block ent[j] of A's own value array -- the
+// same storage as the copy's block j, p.block_im_fast being the opposite of A's -- conjugated
+// (and widened to the vectors' type when the operator is the narrower one, both exact) at the
+// load.  Entries in list order (ascending nonzero index of A: the copy's order), the bd elements
+// ascending, Ops<>::fma on the same operands: the bits of the generic kernel on the conjugated
+// copy, and the same from run to run.  A block column with no entry writes alpha * 0 (plus y
+// when adding).  Every offset into v, x and y is 64-bit.
+template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
+    if constexpr (std::is_same<EX, EV>::value) return a;
+    else return widen(a);
+}
+
+template <typename EV, typename EX, bool YROW, bool XROW>
+__global__ void __launch_bounds__(256) bsr_adj_kernel(const BsrArgs p, const int *__restrict__ ent) {
+    const int bi = p.bi, bd = p.bd;
+    const long total = p.block_rows * bi * p.ncols;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EX *__restrict__ x = (const EX *)p.x;
+    EX *__restrict__ y = (EX *)p.y;
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
+        long i, col;
+        int c;
+        if (YROW) {
+            col = idx % p.ncols;
+            const long t = idx / p.ncols;
+            c = (int)(t % bi);
+            i = t / bi;
+        } else {
+            c = (int)(idx % bi);
+            const long t = idx / bi;
+            i = t % p.block_rows;
+            col = t / p.block_rows;
+        }
+        EX acc = Ops<EX>::zero();
+        const int j0 = p.ii[i], j1 = p.ii[i + 1];
+        for (int j = j0; j < j1; ++j) {
+            const long d0 = p.jj[j];
+            const EV *vb = v + (long)ent[j] * bi * bd;
+            for (int e = 0; e < bd; ++e) {
+                const EX a = to_vec<EX>(Ops<EV>::conj(p.block_im_fast ? vb[c + (long)e * bi] : vb[(long)c * bd + e]));
+                const EX xv = XROW ? x[(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
+                acc = Ops<EX>::fma(a, xv, acc);
+            }
+        }
+        const long img = i * bi + c;
+        EX *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
+        const EX out = Ops<EX>::scale(acc, p.alpha_re, p.alpha_im);
+        *yp = p.add ? Ops<EX>::add(*yp, out) : out;
+    }
+}
+
+/// The in-place adjoint of a plain operator: the matrix-core form where launch_typed's
+/// dense-block clause would take the copy (same-type products; not 3x3 and 12x12 blocks, whose
+/// LDS-DMA kernels stream contiguous value runs that an indirection breaks), else the generic form.
+template <typename EV, typename EX>
+void launch_adj(const BsrArgs &a, const int *ent, bool yrow, bool xrow, hipStream_t s) {
+    if constexpr (std::is_same<EV, EX>::value) {
+        if (!(a.bi == 3 && a.bd == 3) && !(a.bi == 12 && a.bd == 12) && blk_mfma_admits(a) &&
+            launch_blk<EX>(a, yrow, xrow, s, ent))
+            return;
+    }
+    const long total = a.block_rows * a.bi * a.ncols;
+    const long blocks = std::min((total + 255) / 256, 65536L);
+    g_bsr_tune.last = 18;
+    KernelTimer timer("bsr", s);
+    if (yrow && xrow)
+        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, true, true>), dim3(blocks), dim3(256), 0, s, a, ent);
+    else if (yrow && !xrow)
+        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, true, false>), dim3(blocks), dim3(256), 0, s, a, ent);
+    else if (!yrow && xrow)
+        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, false, true>), dim3(blocks), dim3(256), 0, s, a, ent);
+    else
+        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, false, false>), dim3(blocks), dim3(256), 0, s, a, ent);
+    SBX_HIP_CHECK(hipGetLastError());
 }
 
 template <typename E> __device__ __forceinline__ E conj_of(E v) { return v; }
@@ -2074,6 +2360,20 @@ void launch_bsr(const BsrDesc &d, int device) {
     a.nt = g_bsr_tune.nt;
     a.tiles[0] = d.tiles[0];
     a.tiles[1] = d.tiles[1];
+    if (d.adj_ent) {
+        // the adjoint of a plain operator on A's own values (bsr.adj_inplace)
+        const bool yr = d.y_row_major, xr = d.x_row_major;
+        if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_adj<float2, double2>(a, d.adj_ent, yr, xr, s);
+        if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_adj<float, double>(a, d.adj_ent, yr, xr, s);
+        if (d.tv != d.t) throw Error("bsr: unsupported pair of value and vector types");
+        switch (d.t) {
+        case SBX_CDOUBLE: return launch_adj<double2, double2>(a, d.adj_ent, yr, xr, s);
+        case SBX_CFLOAT: return launch_adj<float2, float2>(a, d.adj_ent, yr, xr, s);
+        case SBX_DOUBLE: return launch_adj<double, double>(a, d.adj_ent, yr, xr, s);
+        case SBX_FLOAT: return launch_adj<float, float>(a, d.adj_ent, yr, xr, s);
+        default: throw Error("bsr: unsupported type");
+        }
+    }
     if (d.tv != d.t) {
         // single-precision values, double-precision vectors (bsr_krylov admits these two pairs)
         if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE)

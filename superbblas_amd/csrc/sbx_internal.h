@@ -340,6 +340,17 @@ struct BsrTune {
                    ///< 1024 elements and more at any column count, smaller ones from 4 rhs columns;
                    ///< blk_mfma 2: at any column count), 0 = every mixed product on the generic
                    ///< mixed kernel
+    int adj_inplace = 0; ///< A^H of operators made by create_bsr (x with the image labels), read at
+                         ///< each product: 0 = through a conjugated, regrouped copy of the value
+                         ///< blocks made at the first such product (a snapshot; A's own kernels
+                         ///< run on it), 1 = A's value array read in place through an entry list
+                         ///< (4 bytes per nonzero block): no copy, A^H follows in-place changes of
+                         ///< the values as A does (last_kernel 17 / 18; 3x3 and 12x12 operators
+                         ///< give up their LDS-DMA kernels for it).  Kronecker operators ignore it
+                         ///< (always in place)
+    /// read-back ("bsr.adj_copy_bytes"): bytes held by the value copies of transposed operators,
+    /// process-wide (grows when a copy is made, shrinks when its operator is destroyed)
+    std::atomic<long long> adj_copy_bytes{0};
     /// read-back ("bsr.last_kernel"; atomic: launches may come from several host threads): the form
     /// of the last launch -- 1 one thread per block (3x3), 2 split rows (3x3), 3 row chunks (3x3),
     /// 4 site tiles (3x3),
@@ -351,6 +362,8 @@ struct BsrTune {
     /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element -- or, with
     /// last_mixed 1 (Kronecker operators are never mixed), dense blocks with single-precision
     /// values and double-precision vectors on MFMA (bsr_blk_mfma_mixed_kernel),
+    /// 17 the in-place adjoint of dense blocks on MFMA (bsr_blk_mfma_adj_kernel), 18 the in-place
+    /// adjoint, a thread per output element (bsr_adj_kernel),
     /// 0 another kernel
     std::atomic<int> last{0};
     /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type
@@ -436,6 +449,11 @@ struct BsrDesc {
     // of A's, v / kron A's own arrays and num_nnz_per_row A's count; adj_ptr [block_rows + 1]
     // the row pointer over the sites, adj_ent A's nonzero index k = I * nnz + mu per entry
     // (ii / jj unused); x is (A's block row, A's bi, ncols, A's ki), y (site, A's bd, ncols, A's kd)
+    // The in-place adjoint of a plain operator A (kron == nullptr, adj_ent set, bsr.adj_inplace):
+    // ii / jj are the transposed pattern as ever (the row pointer over A's block columns, the
+    // first element of A's block row per entry), v is A's own value array and adj_ent A's nonzero
+    // index per entry: entry q reads block adj_ent[q] of v conj-transposed (block_im_fast is the
+    // opposite of A's: the same storage read transposed); adj_ptr unused
     const int *adj_ptr = nullptr, *adj_ent = nullptr;
     // site tiles of 3x3 9-point operators (bsr.cpp build_tile_schedule): [0] 16-site tiles (the
     // 8-column kernel), [1] 8-site tiles (the 16-column kernel); rows == nullptr: none
