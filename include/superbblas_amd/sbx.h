@@ -124,22 +124,22 @@ int sbx_timings_report(char *buf, int len);
    2 at any column count; 0 the generic kernel; 3x3, 12x12 and Kronecker operators keep their kernels),
    "bsr.mixed" (a float / complex<float> operator applied to double / complex<double> vectors, see
    sbx_bsr_krylov: 1, the default, the dense blocks that "bsr.blk_mfma", "bsr.blk_min" and "bsr.variant" admit
-   on the mixed matrix-core kernel bsr_blk_mfma_mixed_kernel where it was measured faster than the generic
-   mixed kernel -- blocks of 1024 elements and more at any rhs column count, smaller ones from 4 columns;
+   on the matrix-core kernel bsr_blk_mfma_kernel (its mixed form) where it was measured faster than the generic
+   kernel's mixed form -- blocks of 1024 elements and more at any rhs column count, smaller ones from 4 columns;
    "bsr.blk_mfma" 2 at any column count; 0 every mixed product on the generic mixed kernel; never a converted copy),
    "bsr.adj_inplace" (A^H products, x with the image labels, of operators of sbx_create_bsr; read at each
    product: 0, the default, through a conjugated, regrouped copy of the value blocks made at the first such
    product -- a snapshot of the values, and as many bytes again; 1 from A's own value array in place through a
    list of A's nonzero index per entry -- no copy, A^H follows in-place changes of the values as A does, the
-   same bits as the kernels on the copy; the dense blocks "bsr.blk_mfma" admits on bsr_blk_mfma_adj_kernel,
-   everything else, the mixed pairs and 3x3 / 12x12 operators included, on bsr_adj_kernel; Kronecker
+   same bits as the kernels on the copy; the dense blocks "bsr.blk_mfma" admits on bsr_blk_mfma_kernel's adjoint form,
+   everything else, the mixed pairs and 3x3 / 12x12 operators included, on bsr_kernel's; Kronecker
    operators ignore it, they are in place already),
    "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
    last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel; 16 with "bsr.last_mixed" 1 =
-   bsr_blk_mfma_mixed_kernel, 0 with it = the generic mixed kernel; 17 = bsr_blk_mfma_adj_kernel and 18 =
-   bsr_adj_kernel, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
+   its mixed form, 0 with it = the generic kernel bsr_kernel's mixed form; 17 = bsr_blk_mfma_kernel's and 18 =
+   bsr_kernel's adjoint form, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
    by the value copies of transposed operators, process-wide: it grows when a copy is made and shrinks when
    its operator is destroyed; it cannot be set), "bsr.last_mixed" (1 when the last BSR
    launch read values of a narrower type than its vectors, else 0), "dist.peer_copies",

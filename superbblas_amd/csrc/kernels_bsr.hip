@@ -46,14 +46,39 @@ struct BsrArgs {
     TileSched tiles[2];
 };
 
-template <typename E, int BI_, int BD_, bool YROW, bool XROW>
-__global__ void __launch_bounds__(256) bsr_kernel(const BsrArgs p) {
+// A value of the operator's type EV as the vectors' type EX: itself, or an operator kept in
+// single precision (float, float2) widened to the double counterpart (exact)
+__device__ __forceinline__ double widen(float a) { return (double)a; }
+__device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
+template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
+    if constexpr (std::is_same<EX, EV>::value) return a;
+    else return widen(a);
+}
+
+// The generic form, any block size, pattern and layout: one thread per output element, for
+//  * same-type products (EV == EX; BI_, BD_ > 0: a compile-time block shape);
+//  * mixed products: an operator kept in single precision (EV: float, float2) applied to vectors
+//    of the double counterpart (EX).  The values are read in place as EV and widened at the load
+//    (exact); products, sums, alpha and the store of y are FP64.  No converted copy of the
+//    values exists;
+//  * ADJ, the in-place adjoint (bsr.adj_inplace): the transposed pattern with an entry
+//    indirection.  The output element is (block column J of A, component c, rhs column); entry j
+//    of J reads block ent[j] of A's own value array -- the same storage as the copy's block j,
+//    p.block_im_fast being the opposite of A's -- conjugated (and widened, both exact) at the
+//    load.  Entries in list order (ascending nonzero index of A: the copy's order): the bits of
+//    the forward form on the conjugated copy.  A block column with no entry writes alpha * 0
+//    (plus y when adding).
+// Every form takes a row's entries in order and the bd elements ascending with Ops<EX>::fma, so
+// the result is the same from run to run.  Offsets into v, x and y are 64-bit (the forward
+// forms' element offset inside a block is an int below bi * bd).
+template <typename EV, typename EX, int BI_, int BD_, bool YROW, bool XROW, bool ADJ>
+__global__ void __launch_bounds__(256) bsr_kernel(const BsrArgs p, const int *__restrict__ ent) {
     const int bi = BI_ > 0 ? BI_ : p.bi;
     const int bd = BD_ > 0 ? BD_ : p.bd;
     const long total = p.block_rows * bi * p.ncols;
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ x = (const E *)p.x;
-    E *__restrict__ y = (E *)p.y;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EX *__restrict__ x = (const EX *)p.x;
+    EX *__restrict__ y = (EX *)p.y;
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
         long i, col;
         int c;
@@ -68,33 +93,43 @@ __global__ void __launch_bounds__(256) bsr_kernel(const BsrArgs p) {
             i = t % p.block_rows;
             col = t / p.block_rows;
         }
-        E acc = Ops<E>::zero();
+        EX acc = Ops<EX>::zero();
         const int j0 = p.ii[i], j1 = p.ii[i + 1];
         for (int j = j0; j < j1; ++j) {
-            const int d0 = p.jj[j];
-            if (d0 < 0) continue;
-            const E *vb = v + (long)j * bi * bd;
-#pragma unroll
-            for (int e = 0; e < (BD_ > 0 ? BD_ : 1); ++e) {
-                if (BD_ == 0) break;
-                const E a = p.block_im_fast ? vb[c + e * bi] : vb[c * bd + e];
-                const E xv = XROW ? x[(long)(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
-                acc = Ops<E>::fma(a, xv, acc);
-            }
-            if (BD_ == 0) {
-                for (int e = 0; e < bd; ++e) {
-                    const E a = p.block_im_fast ? vb[c + e * bi] : vb[c * bd + e];
-                    const E xv =
-                        XROW ? x[(long)(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
-                    acc = Ops<E>::fma(a, xv, acc);
-                }
+            // The adjoint keeps the 64-bit index arithmetic and the loop without a skip test that
+            // it was measured with (the transposed pattern holds no skipped block): with the
+            // forward form's int indices and its test -- a branch on d0 ahead of the load of
+            // ent[j] -- form 18 was 6-17 % slower (profiles/bsr_kernels_refactor_measure.txt)
+            typedef typename std::conditional<ADJ, long, int>::type K;
+            const K d0 = p.jj[j];
+            if (!ADJ && d0 < 0) continue;
+            const EV *vb = v + (long)(ADJ ? ent[j] : j) * bi * bd;
+            for (int e = 0; e < bd; ++e) { // (BD_ > 0: a compile-time trip count)
+                EV a = p.block_im_fast ? vb[c + (K)e * bi] : vb[(K)c * bd + e];
+                if constexpr (ADJ) a = Ops<EV>::conj(a);
+                const EX xv = XROW ? x[(long)(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
+                acc = Ops<EX>::fma(to_vec<EX>(a), xv, acc);
             }
         }
         const long img = i * bi + c;
-        E *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
-        const E out = Ops<E>::scale(acc, p.alpha_re, p.alpha_im);
-        *yp = p.add ? Ops<E>::add(*yp, out) : out;
+        EX *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
+        const EX out = Ops<EX>::scale(acc, p.alpha_re, p.alpha_im);
+        *yp = p.add ? Ops<EX>::add(*yp, out) : out;
     }
+}
+
+/// The generic form's launch: the kernel of the two layouts
+template <typename EV, typename EX, int BI, int BD, bool ADJ = false>
+void launch_generic(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
+    const long total = a.block_rows * a.bi * a.ncols;
+    const long blocks = std::min((total + 255) / 256, 65536L);
+    KernelTimer timer("bsr", s);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, s, a, ent); };
+    if (yrow && xrow) go(bsr_kernel<EV, EX, BI, BD, true, true, ADJ>);
+    else if (yrow) go(bsr_kernel<EV, EX, BI, BD, true, false, ADJ>);
+    else if (xrow) go(bsr_kernel<EV, EX, BI, BD, false, true, ADJ>);
+    else go(bsr_kernel<EV, EX, BI, BD, false, false, ADJ>);
+    SBX_HIP_CHECK(hipGetLastError());
 }
 
 constexpr int ELL_LDS_BYTES = 24576; // per workgroup: several workgroups share a CU
@@ -257,6 +292,10 @@ template <> struct BsrMfmaElem<double, true> { typedef double2 type; };
 template <> struct BsrMfmaElem<double, false> { typedef double type; };
 template <> struct BsrMfmaElem<float, true> { typedef float2 type; };
 template <> struct BsrMfmaElem<float, false> { typedef float type; };
+// BsrMfmaElem's inverse: the real type and the complexity of an element type
+template <typename E> struct BsrMfmaScalar { typedef E real; static constexpr bool cplx = false; };
+template <> struct BsrMfmaScalar<double2> { typedef double real; static constexpr bool cplx = true; };
+template <> struct BsrMfmaScalar<float2> { typedef float real; static constexpr bool cplx = true; };
 // 16x16x4 MFMA per real type and its C/D row map (col = lane & 15)
 template <typename R> struct BsrMfma;
 template <> struct BsrMfma<double> {
@@ -1385,21 +1424,6 @@ void launch_ell(const BsrArgs &a, int nnz, bool yrow, bool xrow, hipStream_t s) 
     launch_ell_g<E, BI, BD, 2>(a, nnz, yrow, xrow, s, ELL_LDS_BYTES);
 }
 
-template <typename E, int BI, int BD>
-void launch_layouts(const BsrArgs &a, bool yrow, bool xrow, long blocks, hipStream_t s) {
-    KernelTimer timer("bsr", s);
-    if (yrow && xrow)
-        hipLaunchKernelGGL((bsr_kernel<E, BI, BD, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (yrow && !xrow)
-        hipLaunchKernelGGL((bsr_kernel<E, BI, BD, true, false>), dim3(blocks), dim3(256), 0, s, a);
-    else if (!yrow && xrow)
-        hipLaunchKernelGGL((bsr_kernel<E, BI, BD, false, true>), dim3(blocks), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((bsr_kernel<E, BI, BD, false, false>), dim3(blocks), dim3(256), 0, s,
-                           a);
-    SBX_HIP_CHECK(hipGetLastError());
-}
-
 // Dense blocks of 16 x 16 and more (the multigrid coarse operators: (2 nv) x (2 nv) blocks, 9
 // per row, 1-64 rhs columns) on the matrix cores.  One workgroup per block row and group of NT
 // tiles of 16 rhs columns; wave w owns the 16-row strip w % nstrips of the row (at most 8
@@ -1409,7 +1433,7 @@ void launch_layouts(const BsrArgs &a, bool yrow, bool xrow, long blocks, hipStre
 //    The LDS image keeps the VE = 16 / sizeof(E) consecutive k of a column together: a B
 //    fragment of VE k-steps is one 16-byte LDS read;
 //  * a wave reads its strip of the value block straight into A fragments: lane (row r, k-group
-//    kq) takes the VE consecutive k at (4 ss + kq) VE of row r as one 16-byte load (row-major
+//    kq) takes the VA consecutive k at (4 ss + kq) VA of row r as one 16-byte load (row-major
 //    blocks whose rows are 16-byte multiples; the k order inside a block is free, A and B
 //    agree on it), four such loads in flight -- a block's first four issued before the next x
 //    block is staged (48x48 complex<float> n = 12: 203 -> 188 us) -- and applies them to all NT
@@ -1417,518 +1441,52 @@ void launch_layouts(const BsrArgs &a, bool yrow, bool xrow, long blocks, hipStre
 //    are read as 16-element column runs, ragged tails element by element, never past the block;
 //  * rows of one or two strips split the k-steps of a block over 4 / 2 waves (kparts); the
 //    partial tiles are summed through LDS in wave order, so the result has one fixed order.
-// No LDS-DMA (no check_dma_lds), no atomics; every offset into v, x and y is 64-bit.
+// No LDS-DMA (no check_dma_lds), no atomics; every offset into v, x and y is 64-bit; the 16-byte
+// value load only where all of it lies inside the row (k0 + VA <= bd) of an aligned operator,
+// else by elements.
+//
+// The one kernel serves three forms (bsr.last_kernel), the differences under if constexpr:
+//  * 14, the same-type product: values and vectors of type E = (R, CPLX), VA = VE, H = 1;
+//  * 16, the mixed product (RV = float, R = double): an operator kept in single precision
+//    applied to double-precision vectors on v_mfma_f64_16x16x4_f64.  The value fragments are
+//    read in the operator's type EV: lane (row r, k-group kq) reads the VA = 16 / sizeof(EV)
+//    consecutive k at (4 ss + kq) VA of row r as one 16-byte load (2 complex<float>, 4 float) and
+//    widens them (exact) in registers just before the MFMAs, so a fragment in flight is 4 VGPRs
+//    as in the same-type product; no converted copy of the values exists.  x is staged in LDS as
+//    doubles and B keeps A's k order: lane (column c, kq) takes the same VA k of column c, 32
+//    bytes, as H = VA / VE = 2 16-byte reads.  LDS banks (ds_read_b128 serves a wave in four
+//    16-lane groups, each holding every column once with two values of kq; bank (a / 4) mod 64,
+//    a 256-byte row of sixteen 16-byte slots): with the 32 bytes adjacent, a read's slot is
+//    2 c (+ 1) mod 16 -- columns c and c + 8 of a lane group on one slot, a 2-way conflict on
+//    every read.  So the H pieces of a group lie XW slots apart, image [k-group][piece][column]:
+//    the slot of a read is c mod 16, every lane group covers the 16 slots once, no conflict.
+//    (For either pair that is the same-type image of the double type; H = 1 gives form 14's.)
+//  * 17, ADJ, the in-place adjoint (bsr.adj_inplace): the transposed operator's pattern over A's
+//    own value array.  Entry j of a block row reads block ent[j] of A instead of block j of the
+//    copy, and the imaginary parts are negated in registers as a fragment is loaded (real types
+//    load unchanged; the zeros of the padding are never loaded and stay as they are): the bytes
+//    read per block are the copy's, plus the 4 of ent[j].  The block is A's storage read in the
+//    flipped order (p.block_im_fast is the opposite of A's), so A's row-major blocks are the
+//    image-fastest case here, exactly as on the copy, and the 16-byte loads apply where they
+//    would on the copy and A's array is 16-byte aligned.  Entries are in ascending nonzero index
+//    of A within a block column, the copy's order; the conjugation is an exact sign flip and
+//    every other operation is the same, so the result has the bits of form 14 on the copy.
+//    (The template also expresses the mixed in-place adjoint; it is neither instantiated nor
+//    dispatched: mixed pairs take the generic form 18.)
 template <typename E> struct alignas(16) BlkVec { E e[16 / sizeof(E)]; };
 
-template <typename R, bool CPLX, int NT>
-__global__ void __launch_bounds__(512) bsr_blk_mfma_kernel(const BsrArgs p, int yrow, int xrow, int nstrips,
-                                                           int kparts, int vec_ok) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
+template <typename RV, typename R, bool CPLX, int NT, bool ADJ>
+__global__ void __launch_bounds__(512) bsr_blk_mfma_kernel(const BsrArgs p, const int *__restrict__ ent,
+                                                           int yrow, int xrow, int nstrips, int kparts,
+                                                           int vec_ok) {
+    typedef typename BsrMfmaElem<RV, CPLX>::type EV; // the values
+    typedef typename BsrMfmaElem<R, CPLX>::type E;   // the vectors
     typedef typename BsrMfma<R>::acc_t acc_t;
-    typedef BlkVec<E> V;
-    constexpr int VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    E *xs = (E *)smem;
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ x = (const E *)p.x;
-    E *__restrict__ y = (E *)p.y;
-    const int bi = p.bi, bd = p.bd;
-    const int nss = (bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE; // k-steps of 4 VE
-    const int xbuf = kpad * XW;                                        // elements per x buffer
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long i = blockIdx.x, col0 = (long)blockIdx.y * XW;
-    const bool active = w < nstrips * kparts;
-    const int strip = w % nstrips, kp = w / nstrips;
-    const int ar = lane & 15, kq = lane >> 4;
-    const int arow = strip * 16 + ar;
-    const bool arow_ok = active && arow < bi;
-
-    // staging order: element e = outer * nin + inner, inner the fastest index of x (the rhs
-    // column for row-major x, else the domain row), walked by steps of the workgroup size
-    const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
-    const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
-    auto stage = [&](int j, int buf) {
-        const int dj = p.jj[j];
-        if (dj < 0) return;
-        E *dst = xs + buf * xbuf;
-        int in = in0, out = out0;
-        while (out < nout) {
-            E t[4];
-            int kk[4], cc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                kk[q] = xrow ? out : in;
-                cc[q] = xrow ? in : out;
-                const long col = col0 + cc[q];
-                t[q] = E{};
-                if (out < nout && kk[q] < bd && col < p.ncols)
-                    t[q] = xrow ? x[(long)(dj + kk[q]) * p.ldx + col] : x[(long)(dj + kk[q]) + col * p.ldx];
-                if (out >= nout) kk[q] = -1;
-                in += din;
-                out += dout;
-                if (in >= nin) {
-                    in -= nin;
-                    ++out;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
-        }
-    };
-    auto load_a = [&](const E *vb, int ss) {
-        V a;
-#pragma unroll
-        for (int t = 0; t < VE; ++t) a.e[t] = E{};
-        const int k0 = (ss * 4 + kq) * VE;
-        if (arow_ok && k0 < bd) {
-            if (!p.block_im_fast) {
-                const E *src = vb + (long)arow * bd + k0;
-                if (vec_ok && k0 + VE <= bd) {
-                    a = *(const V *)src;
-                } else {
-#pragma unroll
-                    for (int t = 0; t < VE; ++t)
-                        if (k0 + t < bd) a.e[t] = src[t];
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < VE; ++t)
-                    if (k0 + t < bd) a.e[t] = vb[arow + (long)(k0 + t) * bi];
-            }
-        }
-        return a;
-    };
-    acc_t accR[NT], accI[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
-    auto apply = [&](const V &a, int ss, const E *xb) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const V b = *(const V *)(xb + ((ss * 4 + kq) * XW + nt * 16 + ar) * VE);
-#pragma unroll
-            for (int t = 0; t < VE; ++t) {
-                if constexpr (CPLX) {
-                    accR[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].x, accR[nt]);
-                    accI[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].y, accI[nt]);
-                    accR[nt] = BsrMfma<R>::mma(-a.e[t].y, b.e[t].y, accR[nt]);
-                    accI[nt] = BsrMfma<R>::mma(a.e[t].y, b.e[t].x, accI[nt]);
-                } else {
-                    accR[nt] = BsrMfma<R>::mma(a.e[t], b.e[t], accR[nt]);
-                }
-            }
-        }
-    };
-
-    const int jb = p.ii[i], je = p.ii[i + 1];
-    if (jb < je) stage(jb, 0);
-    __syncthreads();
-    for (int j = jb; j < je; ++j) {
-        const int buf = (j - jb) & 1;
-        const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
-        const E *vb = v + (long)j * bi * bd;
-        const E *xb = xs + buf * xbuf;
-        // the block's first U fragments are in flight while the next x block is staged
-        V a[U];
-        if (on) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) a[u] = load_a(vb, kp + u * kparts);
-        }
-        if (j + 1 < je) stage(j + 1, buf ^ 1);
-        if (on) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (kp + u * kparts < nss) apply(a[u], kp + u * kparts, xb);
-            for (int ss = kp + U * kparts; ss < nss; ss += U * kparts) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = load_a(vb, ss + u * kparts);
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (ss + u * kparts < nss) apply(a[u], ss + u * kparts, xb);
-            }
-        }
-        __syncthreads(); // buffer buf is free again, buffer buf ^ 1 is complete
-    }
-    if (kparts > 1) {
-        // the x buffers are dead (every path above ends in a barrier): partial tiles of the
-        // k-parts 1.. to LDS, summed by part 0 in part order
-        R *red = (R *)smem;
-        if (active && kp > 0) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    red[(((w * NT + nt) * NC + 0) * 4 + q) * 64 + lane] = accR[nt][q];
-                    if constexpr (CPLX) red[(((w * NT + nt) * NC + 1) * 4 + q) * 64 + lane] = accI[nt][q];
-                }
-        }
-        __syncthreads();
-        if (active && kp == 0) {
-            for (int k2 = 1; k2 < kparts; ++k2) {
-                const int w2 = strip + k2 * nstrips;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        accR[nt][q] += red[(((w2 * NT + nt) * NC + 0) * 4 + q) * 64 + lane];
-                        if constexpr (CPLX) accI[nt][q] += red[(((w2 * NT + nt) * NC + 1) * 4 + q) * 64 + lane];
-                    }
-            }
-        }
-    }
-    if (!active || kp != 0) return;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = strip * 16 + BsrMfma<R>::row(lane, q);
-            const long col = col0 + nt * 16 + ar;
-            if (row >= bi || col >= p.ncols) continue;
-            const long img = i * bi + row;
-            E *yp = yrow ? y + img * p.ldy + col : y + img + col * p.ldy;
-            E out;
-            if constexpr (CPLX)
-                out = Ops<E>::scale(E{accR[nt][q], accI[nt][q]}, p.alpha_re, p.alpha_im);
-            else
-                out = Ops<E>::scale(accR[nt][q], p.alpha_re, p.alpha_im);
-            *yp = p.add ? Ops<E>::add(*yp, out) : out;
-        }
-}
-
-// The in-place adjoint on the matrix cores (bsr.adj_inplace): bsr_blk_mfma_kernel, line by line,
-// on the transposed operator's pattern over A's own value array.  Entry j of a block row reads
-// block ent[j] of A instead of block j of the copy, and the imaginary parts are negated in
-// registers as a fragment is loaded (real types load unchanged; the zeros of the padding are
-// never loaded and stay as they are): the bytes read per block are the copy's, plus the 4 of
-// ent[j].  The block is A's storage read in the flipped order (p.block_im_fast is the opposite of
-// A's), so A's row-major blocks are the image-fastest case here, exactly as on the copy, and the
-// 16-byte loads apply where they would on the copy and A's array is 16-byte aligned.  Entries are
-// in ascending nonzero index of A within a block column, the copy's order; the conjugation is an
-// exact sign flip and every other operation is the same, so the result has the bits of
-// bsr_blk_mfma_kernel on the copy.  No LDS-DMA, no atomics; every offset into v, x and y is 64-bit.
-template <typename R, bool CPLX, int NT>
-__global__ void __launch_bounds__(512) bsr_blk_mfma_adj_kernel(const BsrArgs p, const int *__restrict__ ent,
-                                                               int yrow, int xrow, int nstrips, int kparts,
-                                                               int vec_ok) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
-    typedef typename BsrMfma<R>::acc_t acc_t;
-    typedef BlkVec<E> V;
-    constexpr int VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    E *xs = (E *)smem;
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ x = (const E *)p.x;
-    E *__restrict__ y = (E *)p.y;
-    const int bi = p.bi, bd = p.bd;
-    const int nss = (bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE; // k-steps of 4 VE
-    const int xbuf = kpad * XW;                                        // elements per x buffer
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long i = blockIdx.x, col0 = (long)blockIdx.y * XW;
-    const bool active = w < nstrips * kparts;
-    const int strip = w % nstrips, kp = w / nstrips;
-    const int ar = lane & 15, kq = lane >> 4;
-    const int arow = strip * 16 + ar;
-    const bool arow_ok = active && arow < bi;
-
-    // staging order: element e = outer * nin + inner, inner the fastest index of x (the rhs
-    // column for row-major x, else the domain row), walked by steps of the workgroup size
-    const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
-    const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
-    auto stage = [&](int j, int buf) {
-        const int dj = p.jj[j];
-        if (dj < 0) return;
-        E *dst = xs + buf * xbuf;
-        int in = in0, out = out0;
-        while (out < nout) {
-            E t[4];
-            int kk[4], cc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                kk[q] = xrow ? out : in;
-                cc[q] = xrow ? in : out;
-                const long col = col0 + cc[q];
-                t[q] = E{};
-                if (out < nout && kk[q] < bd && col < p.ncols)
-                    t[q] = xrow ? x[(long)(dj + kk[q]) * p.ldx + col] : x[(long)(dj + kk[q]) + col * p.ldx];
-                if (out >= nout) kk[q] = -1;
-                in += din;
-                out += dout;
-                if (in >= nin) {
-                    in -= nin;
-                    ++out;
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
-        }
-    };
-    auto load_a = [&](const E *vb, int ss) {
-        V a;
-#pragma unroll
-        for (int t = 0; t < VE; ++t) a.e[t] = E{};
-        const int k0 = (ss * 4 + kq) * VE;
-        if (arow_ok && k0 < bd) {
-            if (!p.block_im_fast) {
-                const E *src = vb + (long)arow * bd + k0;
-                if (vec_ok && k0 + VE <= bd) {
-                    a = *(const V *)src;
-#pragma unroll
-                    for (int t = 0; t < VE; ++t) a.e[t] = Ops<E>::conj(a.e[t]);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < VE; ++t)
-                        if (k0 + t < bd) a.e[t] = Ops<E>::conj(src[t]);
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < VE; ++t)
-                    if (k0 + t < bd) a.e[t] = Ops<E>::conj(vb[arow + (long)(k0 + t) * bi]);
-            }
-        }
-        return a;
-    };
-    acc_t accR[NT], accI[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
-    auto apply = [&](const V &a, int ss, const E *xb) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const V b = *(const V *)(xb + ((ss * 4 + kq) * XW + nt * 16 + ar) * VE);
-#pragma unroll
-            for (int t = 0; t < VE; ++t) {
-                if constexpr (CPLX) {
-                    accR[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].x, accR[nt]);
-                    accI[nt] = BsrMfma<R>::mma(a.e[t].x, b.e[t].y, accI[nt]);
-                    accR[nt] = BsrMfma<R>::mma(-a.e[t].y, b.e[t].y, accR[nt]);
-                    accI[nt] = BsrMfma<R>::mma(a.e[t].y, b.e[t].x, accI[nt]);
-                } else {
-                    accR[nt] = BsrMfma<R>::mma(a.e[t], b.e[t], accR[nt]);
-                }
-            }
-        }
-    };
-
-    const int jb = p.ii[i], je = p.ii[i + 1];
-    if (jb < je) stage(jb, 0);
-    __syncthreads();
-    for (int j = jb; j < je; ++j) {
-        const int buf = (j - jb) & 1;
-        const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
-        const E *vb = v + (long)ent[j] * bi * bd; // (wave-uniform)
-        const E *xb = xs + buf * xbuf;
-        // the block's first U fragments are in flight while the next x block is staged
-        V a[U];
-        if (on) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) a[u] = load_a(vb, kp + u * kparts);
-        }
-        if (j + 1 < je) stage(j + 1, buf ^ 1);
-        if (on) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-                if (kp + u * kparts < nss) apply(a[u], kp + u * kparts, xb);
-            for (int ss = kp + U * kparts; ss < nss; ss += U * kparts) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) a[u] = load_a(vb, ss + u * kparts);
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (ss + u * kparts < nss) apply(a[u], ss + u * kparts, xb);
-            }
-        }
-        __syncthreads(); // buffer buf is free again, buffer buf ^ 1 is complete
-    }
-    if (kparts > 1) {
-        // the x buffers are dead (every path above ends in a barrier): partial tiles of the
-        // k-parts 1.. to LDS, summed by part 0 in part order
-        R *red = (R *)smem;
-        if (active && kp > 0) {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    red[(((w * NT + nt) * NC + 0) * 4 + q) * 64 + lane] = accR[nt][q];
-                    if constexpr (CPLX) red[(((w * NT + nt) * NC + 1) * 4 + q) * 64 + lane] = accI[nt][q];
-                }
-        }
-        __syncthreads();
-        if (active && kp == 0) {
-            for (int k2 = 1; k2 < kparts; ++k2) {
-                const int w2 = strip + k2 * nstrips;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        accR[nt][q] += red[(((w2 * NT + nt) * NC + 0) * 4 + q) * 64 + lane];
-                        if constexpr (CPLX) accI[nt][q] += red[(((w2 * NT + nt) * NC + 1) * 4 + q) * 64 + lane];
-                    }
-            }
-        }
-    }
-    if (!active || kp != 0) return;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int row = strip * 16 + BsrMfma<R>::row(lane, q);
-            const long col = col0 + nt * 16 + ar;
-            if (row >= bi || col >= p.ncols) continue;
-            const long img = i * bi + row;
-            E *yp = yrow ? y + img * p.ldy + col : y + img + col * p.ldy;
-            E out;
-            if constexpr (CPLX)
-                out = Ops<E>::scale(E{accR[nt][q], accI[nt][q]}, p.alpha_re, p.alpha_im);
-            else
-                out = Ops<E>::scale(accR[nt][q], p.alpha_re, p.alpha_im);
-            *yp = p.add ? Ops<E>::add(*yp, out) : out;
-        }
-}
-
-/// false: not this shape (the generic kernel runs).  Limits: bi <= 128 (8 strips, one wave each),
-/// two x buffers of 16 columns within 64 KB of LDS (bd <= 128 for complex<double>, 256 for
-/// 8-byte and 512 for 4-byte elements), at most 65535 groups of NT column tiles.
-/// ent: the in-place adjoint (bsr_blk_mfma_adj_kernel), under the same limits.
-template <typename R, bool CPLX>
-bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
-    constexpr int ES = (int)sizeof(E), VE = 16 / ES;
-    const int nstrips = (a.bi + 15) / 16;
-    if (nstrips > 8 || a.block_rows >= (1L << 31)) return false;
-    const int nss = (a.bd + 4 * VE - 1) / (4 * VE), kpad = nss * 4 * VE;
-    const int kparts = std::min(nstrips == 1 ? 4 : nstrips == 2 ? 2 : 1, nss);
-    const int nw = nstrips * kparts;
-    auto lds_of = [&](int nt) {
-        const long xb = 2L * kpad * nt * 16 * ES;
-        const long red = kparts > 1 ? (long)nw * nt * (CPLX ? 2 : 1) * 4 * 64 * (long)sizeof(R) : 0;
-        return std::max(xb, red);
-    };
-    // NT column tiles share the value fragments; within 32 KB of LDS where that keeps NT > 1
-    // (several workgroups per CU hide the value stream's latency)
-    int nt = a.ncols <= 16 ? 1 : a.ncols <= 32 ? 2 : 4;
-    while (nt > 1 && lds_of(nt) > 32768) nt /= 2;
-    const long lds = lds_of(nt);
-    if (lds > 65536) return false;
-    const long ngroups = (a.ncols + nt * 16 - 1) / (nt * 16);
-    if (ngroups > 65535) return false;
-    const int vec_ok = ((long)a.bd * ES) % 16 == 0 && ((size_t)a.v & 15) == 0 ? 1 : 0;
-    g_bsr_tune.last = ent ? 17 : 14;
-    KernelTimer timer("bsr", s);
-    auto go_adj = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
-                           ent, yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
-    };
-    if (ent) {
-        if (nt == 1) go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 1>);
-        else if (nt == 2) go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 2>);
-        else go_adj(bsr_blk_mfma_adj_kernel<R, CPLX, 4>);
-        SBX_HIP_CHECK(hipGetLastError());
-        return true;
-    }
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
-                           yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
-    };
-    if (nt == 1) go(bsr_blk_mfma_kernel<R, CPLX, 1>);
-    else if (nt == 2) go(bsr_blk_mfma_kernel<R, CPLX, 2>);
-    else go(bsr_blk_mfma_kernel<R, CPLX, 4>);
-    SBX_HIP_CHECK(hipGetLastError());
-    return true;
-}
-
-// Mixed products: an operator kept in single precision (EV: float, float2) applied to vectors of
-// the double counterpart (EX: double, double2).  The values are read in place as EV and widened
-// at the load (exact); products, sums, alpha and the store of y are FP64.  No converted copy of
-// the values exists.
-__device__ __forceinline__ double widen(float a) { return (double)a; }
-__device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
-
-// Generic mixed form: bsr_kernel with separate value and vector types, any block size and
-// pattern; one thread per output element.
-template <typename EV, typename EX, bool YROW, bool XROW>
-__global__ void __launch_bounds__(256) bsr_mixed_kernel(const BsrArgs p) {
-    const int bi = p.bi, bd = p.bd;
-    const long total = p.block_rows * bi * p.ncols;
-    const EV *__restrict__ v = (const EV *)p.v;
-    const EX *__restrict__ x = (const EX *)p.x;
-    EX *__restrict__ y = (EX *)p.y;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
-        long i, col;
-        int c;
-        if (YROW) {
-            col = idx % p.ncols;
-            const long t = idx / p.ncols;
-            c = (int)(t % bi);
-            i = t / bi;
-        } else {
-            c = (int)(idx % bi);
-            const long t = idx / bi;
-            i = t % p.block_rows;
-            col = t / p.block_rows;
-        }
-        EX acc = Ops<EX>::zero();
-        const int j0 = p.ii[i], j1 = p.ii[i + 1];
-        for (int j = j0; j < j1; ++j) {
-            const int d0 = p.jj[j];
-            if (d0 < 0) continue;
-            const EV *vb = v + (long)j * bi * bd;
-            for (int e = 0; e < bd; ++e) {
-                const EX a = widen(p.block_im_fast ? vb[c + (long)e * bi] : vb[(long)c * bd + e]);
-                const EX xv = XROW ? x[(long)(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
-                acc = Ops<EX>::fma(a, xv, acc);
-            }
-        }
-        const long img = i * bi + c;
-        EX *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
-        const EX out = Ops<EX>::scale(acc, p.alpha_re, p.alpha_im);
-        *yp = p.add ? Ops<EX>::add(*yp, out) : out;
-    }
-}
-
-template <typename EV, typename EX>
-void launch_mixed_generic(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
-    const long total = a.block_rows * a.bi * a.ncols;
-    const long blocks = std::min((total + 255) / 256, 65536L);
-    KernelTimer timer("bsr", s);
-    if (yrow && xrow)
-        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, true, true>), dim3(blocks), dim3(256), 0, s, a);
-    else if (yrow && !xrow)
-        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, true, false>), dim3(blocks), dim3(256), 0, s, a);
-    else if (!yrow && xrow)
-        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, false, true>), dim3(blocks), dim3(256), 0, s, a);
-    else
-        hipLaunchKernelGGL((bsr_mixed_kernel<EV, EX, false, false>), dim3(blocks), dim3(256), 0, s, a);
-    SBX_HIP_CHECK(hipGetLastError());
-}
-
-// Matrix-core mixed form: bsr_blk_mfma_kernel's structure (one workgroup per block row and
-// group of NT column tiles, a wave per 16-row strip and k-part, U = 4 value loads in flight with
-// the next x block staged behind them, k-parts summed through LDS in wave order) on
-// v_mfma_f64_16x16x4_f64, with the value fragments read in the operator's type:
-//  * lane (row r, k-group kq) reads the VA = 16 / sizeof(EV) consecutive k at (4 ss + kq) VA of
-//    row r as one 16-byte load (2 complex<float>, 4 float) and widens them in registers just
-//    before the MFMAs, so a fragment in flight is 4 VGPRs as in the same-type kernel;
-//  * x is staged in LDS as doubles and B keeps A's k order: lane (column c, kq) takes the same VA
-//    k of column c, 32 bytes, as two 16-byte reads.  LDS banks (ds_read_b128 serves a wave in
-//    four 16-lane groups, each holding every column once with two values of kq; bank (a / 4) mod
-//    64, a 256-byte row of sixteen 16-byte slots): with the 32 bytes adjacent, a read's slot is
-//    2 c (+ 1) mod 16 -- columns c and c + 8 of a lane group on one slot, a 2-way conflict on every
-//    read.  So the two halves of a group lie XW slots apart, image [k-group][half][column]: the
-//    slot of a read is c mod 16, every lane group covers the 16 slots once, no conflict.  (For
-//    either pair that is the same-type kernel's image of the double type.)
-// No LDS-DMA, no atomics; every offset into v, x and y is 64-bit; the 16-byte value load only
-// where all of it lies inside the row (k0 + VA <= bd) of an aligned operator, else by elements.
-template <bool CPLX, int NT>
-__global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p, int yrow, int xrow, int nstrips,
-                                                                 int kparts, int vec_ok) {
-    typedef typename BsrMfmaElem<float, CPLX>::type EV;
-    typedef typename BsrMfmaElem<double, CPLX>::type E;
-    typedef BsrMfma<double>::acc_t acc_t;
     typedef BlkVec<EV> VV;
     typedef BlkVec<E> V;
-    constexpr int VA = 16 / (int)sizeof(EV), VE = 16 / (int)sizeof(E), XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
-    static_assert(VA == 2 * VE, "a group of VA k is two 16-byte pieces of x");
+    constexpr int VA = 16 / (int)sizeof(EV), VE = 16 / (int)sizeof(E), H = VA / VE;
+    constexpr int XW = NT * 16, NC = CPLX ? 2 : 1, U = 4;
+    static_assert(VA == H * VE, "a group of VA k is H 16-byte pieces of x");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     E *xs = (E *)smem;
     const EV *__restrict__ v = (const EV *)p.v;
@@ -1946,8 +1504,8 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
     const int arow = strip * 16 + ar;
     const bool arow_ok = active && arow < bi;
 
-    // staging as in bsr_blk_mfma_kernel: element e = outer * nin + inner, inner the fastest
-    // index of x, walked by steps of the workgroup size; image [k / VE][column][k % VE]
+    // staging order: element e = outer * nin + inner, inner the fastest index of x (the rhs
+    // column for row-major x, else the domain row), walked by steps of the workgroup size
     const int nin = xrow ? XW : kpad, nout = xrow ? kpad : XW;
     const int in0 = tid % nin, out0 = tid / nin, din = nthr % nin, dout = nthr / nin;
     auto stage = [&](int j, int buf) {
@@ -1979,6 +1537,8 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
                 if (kk[q] >= 0) dst[((kk[q] / VE) * XW + cc[q]) * VE + (kk[q] % VE)] = t[q];
         }
     };
+    // (ADJ conjugates in the element loads' own expressions: written as statements after the
+    // loads, the complex<double> adjoint compiles differently, profiles/bsr_kernels_refactor_isa.txt)
     auto load_a = [&](const EV *vb, int ss) {
         VV a;
 #pragma unroll
@@ -1989,15 +1549,25 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
                 const EV *src = vb + (long)arow * bd + k0;
                 if (vec_ok && k0 + VA <= bd) {
                     a = *(const VV *)src;
+                    if constexpr (ADJ) {
+#pragma unroll
+                        for (int t = 0; t < VA; ++t) a.e[t] = Ops<EV>::conj(a.e[t]);
+                    }
                 } else {
 #pragma unroll
                     for (int t = 0; t < VA; ++t)
-                        if (k0 + t < bd) a.e[t] = src[t];
+                        if (k0 + t < bd) {
+                            if constexpr (ADJ) a.e[t] = Ops<EV>::conj(src[t]);
+                            else a.e[t] = src[t];
+                        }
                 }
             } else {
 #pragma unroll
                 for (int t = 0; t < VA; ++t)
-                    if (k0 + t < bd) a.e[t] = vb[arow + (long)(k0 + t) * bi];
+                    if (k0 + t < bd) {
+                        if constexpr (ADJ) a.e[t] = Ops<EV>::conj(vb[arow + (long)(k0 + t) * bi]);
+                        else a.e[t] = vb[arow + (long)(k0 + t) * bi];
+                    }
             }
         }
         return a;
@@ -2006,24 +1576,24 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) accR[nt] = accI[nt] = acc_t{0, 0, 0, 0};
     auto apply = [&](const VV &af, int ss, const E *xb) {
-        E a[VA]; // the up-conversion: exact
+        E a[VA]; // (the mixed product's up-conversion: exact)
 #pragma unroll
-        for (int t = 0; t < VA; ++t) a[t] = widen(af.e[t]);
+        for (int t = 0; t < VA; ++t) a[t] = to_vec<E>(af.e[t]);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const V b = *(const V *)(xb + (((ss * 4 + kq) * 2 + h) * XW + nt * 16 + ar) * VE);
+            for (int h = 0; h < H; ++h) {
+                const V b = *(const V *)(xb + (((ss * 4 + kq) * H + h) * XW + nt * 16 + ar) * VE);
 #pragma unroll
                 for (int u = 0; u < VE; ++u) {
                     const E ak = a[h * VE + u];
                     if constexpr (CPLX) {
-                        accR[nt] = BsrMfma<double>::mma(ak.x, b.e[u].x, accR[nt]);
-                        accI[nt] = BsrMfma<double>::mma(ak.x, b.e[u].y, accI[nt]);
-                        accR[nt] = BsrMfma<double>::mma(-ak.y, b.e[u].y, accR[nt]);
-                        accI[nt] = BsrMfma<double>::mma(ak.y, b.e[u].x, accI[nt]);
+                        accR[nt] = BsrMfma<R>::mma(ak.x, b.e[u].x, accR[nt]);
+                        accI[nt] = BsrMfma<R>::mma(ak.x, b.e[u].y, accI[nt]);
+                        accR[nt] = BsrMfma<R>::mma(-ak.y, b.e[u].y, accR[nt]);
+                        accI[nt] = BsrMfma<R>::mma(ak.y, b.e[u].x, accI[nt]);
                     } else {
-                        accR[nt] = BsrMfma<double>::mma(ak, b.e[u], accR[nt]);
+                        accR[nt] = BsrMfma<R>::mma(ak, b.e[u], accR[nt]);
                     }
                 }
             }
@@ -2036,7 +1606,7 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
     for (int j = jb; j < je; ++j) {
         const int buf = (j - jb) & 1;
         const bool on = active && p.jj[j] >= 0; // wave-uniform: the MFMAs run with all 64 lanes
-        const EV *vb = v + (long)j * bi * bd;
+        const EV *vb = v + (long)(ADJ ? ent[j] : j) * bi * bd; // (wave-uniform)
         const E *xb = xs + buf * xbuf;
         // the block's first U fragments are in flight while the next x block is staged
         VV a[U];
@@ -2062,7 +1632,7 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
     if (kparts > 1) {
         // the x buffers are dead (every path above ends in a barrier): partial tiles of the
         // k-parts 1.. to LDS, summed by part 0 in part order
-        double *red = (double *)smem;
+        R *red = (R *)smem;
         if (active && kp > 0) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -2091,7 +1661,7 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const int row = strip * 16 + BsrMfma<double>::row(lane, q);
+            const int row = strip * 16 + BsrMfma<R>::row(lane, q);
             const long col = col0 + nt * 16 + ar;
             if (row >= bi || col >= p.ncols) continue;
             const long img = i * bi + row;
@@ -2105,15 +1675,19 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_mixed_kernel(const BsrArgs p
         }
 }
 
-/// false: not this shape (the generic mixed kernel runs).  Limits as launch_bsr_blk_mfma, by the
-/// vector type: bi <= 128, two x buffers of kpad x 16 NT doubles within 64 KB of LDS (kpad: bd
-/// rounded up to 4 VA; bd <= 128 for complex<double> and 256 for double vectors), NT reduced to
+/// false: not this shape (the generic kernel runs).  Values RV, vectors R (the same, or float
+/// values and double vectors: form 16).  Limits, by the vector type: bi <= 128 (8 strips, one wave
+/// each), two x buffers of kpad x 16 columns within 64 KB of LDS (kpad: bd rounded up to 4 VA; bd
+/// <= 128 for complex<double>, 256 for 8-byte and 512 for 4-byte vector elements), NT reduced to
 /// stay within 32 KB where possible, at most 65535 groups of NT column tiles.
-template <bool CPLX>
-bool launch_bsr_blk_mfma_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
-    typedef typename BsrMfmaElem<float, CPLX>::type EV;
-    typedef typename BsrMfmaElem<double, CPLX>::type E;
+/// ent: the in-place adjoint (form 17; same-type products), under the same limits.
+template <typename RV, typename R, bool CPLX>
+bool launch_bsr_blk_mfma(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent) {
+    typedef typename BsrMfmaElem<RV, CPLX>::type EV;
+    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    constexpr bool SAME = std::is_same<RV, R>::value;
     constexpr int ES = (int)sizeof(E), VA = 16 / (int)sizeof(EV);
+    if (ent && !SAME) return false; // the mixed in-place adjoint is not instantiated
     const int nstrips = (a.bi + 15) / 16;
     if (nstrips > 8 || a.block_rows >= (1L << 31)) return false;
     const int nss = (a.bd + 4 * VA - 1) / (4 * VA), kpad = nss * 4 * VA;
@@ -2121,9 +1695,11 @@ bool launch_bsr_blk_mfma_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream
     const int nw = nstrips * kparts;
     auto lds_of = [&](int nt) {
         const long xb = 2L * kpad * nt * 16 * ES;
-        const long red = kparts > 1 ? (long)nw * nt * (CPLX ? 2 : 1) * 4 * 64 * (long)sizeof(double) : 0;
+        const long red = kparts > 1 ? (long)nw * nt * (CPLX ? 2 : 1) * 4 * 64 * (long)sizeof(R) : 0;
         return std::max(xb, red);
     };
+    // NT column tiles share the value fragments; within 32 KB of LDS where that keeps NT > 1
+    // (several workgroups per CU hide the value stream's latency)
     int nt = a.ncols <= 16 ? 1 : a.ncols <= 32 ? 2 : 4;
     while (nt > 1 && lds_of(nt) > 32768) nt /= 2;
     const long lds = lds_of(nt);
@@ -2131,17 +1707,30 @@ bool launch_bsr_blk_mfma_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream
     const long ngroups = (a.ncols + nt * 16 - 1) / (nt * 16);
     if (ngroups > 65535) return false;
     const int vec_ok = ((long)a.bd * (long)sizeof(EV)) % 16 == 0 && ((size_t)a.v & 15) == 0 ? 1 : 0;
-    g_bsr_tune.last = 16;
+    g_bsr_tune.last = ent ? 17 : SAME ? 14 : 16;
     KernelTimer timer("bsr", s);
     auto go = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)a.block_rows, (unsigned)ngroups), dim3(64 * nw), lds, s, a,
-                           yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
+                           ent, yrow ? 1 : 0, xrow ? 1 : 0, nstrips, kparts, vec_ok);
     };
-    if (nt == 1) go(bsr_blk_mfma_mixed_kernel<CPLX, 1>);
-    else if (nt == 2) go(bsr_blk_mfma_mixed_kernel<CPLX, 2>);
-    else go(bsr_blk_mfma_mixed_kernel<CPLX, 4>);
+    auto go_nt = [&](auto adj) {
+        constexpr bool ADJ = SAME && decltype(adj)::value; // (the only adjoints instantiated)
+        if (nt == 1) go(bsr_blk_mfma_kernel<RV, R, CPLX, 1, ADJ>);
+        else if (nt == 2) go(bsr_blk_mfma_kernel<RV, R, CPLX, 2, ADJ>);
+        else go(bsr_blk_mfma_kernel<RV, R, CPLX, 4, ADJ>);
+    };
+    if (ent) go_nt(std::true_type{});
+    else go_nt(std::false_type{});
     SBX_HIP_CHECK(hipGetLastError());
     return true;
+}
+
+/// launch_bsr_blk_mfma by element types: values EV, vectors EX
+template <typename EV, typename EX = EV>
+bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
+    static_assert(BsrMfmaScalar<EV>::cplx == BsrMfmaScalar<EX>::cplx, "both real or both complex");
+    return launch_bsr_blk_mfma<typename BsrMfmaScalar<EV>::real, typename BsrMfmaScalar<EX>::real,
+                               BsrMfmaScalar<EX>::cplx>(a, yrow, xrow, s, ent);
 }
 
 /// A mixed product (values EV, vectors EX).  The matrix-core form takes dense blocks from
@@ -2155,21 +1744,12 @@ bool launch_bsr_blk_mfma_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream
 /// column bound.  3x3 and 12x12 blocks and everything else run the generic mixed form.
 template <typename EV, typename EX>
 void launch_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
-    constexpr bool CPLX = std::is_same<EX, double2>::value;
     if (g_bsr_tune.mixed && g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
         a.bd >= g_bsr_tune.blk_min &&
         a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : 4) &&
-        launch_bsr_blk_mfma_mixed<CPLX>(a, yrow, xrow, s))
+        launch_blk<EV, EX>(a, yrow, xrow, s))
         return;
-    launch_mixed_generic<EV, EX>(a, yrow, xrow, s);
-}
-
-template <typename E>
-bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int *ent = nullptr) {
-    if constexpr (std::is_same<E, double2>::value) return launch_bsr_blk_mfma<double, true>(a, yrow, xrow, s, ent);
-    else if constexpr (std::is_same<E, double>::value) return launch_bsr_blk_mfma<double, false>(a, yrow, xrow, s, ent);
-    else if constexpr (std::is_same<E, float2>::value) return launch_bsr_blk_mfma<float, true>(a, yrow, xrow, s, ent);
-    else return launch_bsr_blk_mfma<float, false>(a, yrow, xrow, s, ent);
+    launch_generic<EV, EX, 0, 0>(a, yrow, xrow, s);
 }
 
 /// Whether launch_typed's dense-block clause takes these blocks at this column count
@@ -2182,26 +1762,16 @@ inline bool blk_mfma_admits(const BsrArgs &a) {
 
 template <typename E>
 void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipStream_t s) {
-    const long total = a.block_rows * a.bi * a.ncols;
-    const long blocks = std::min((total + 255) / 256, 65536L);
     const bool ell = nnz_per_row > 0 &&
                      (long)nnz_per_row * (a.bi * a.bd * (long)sizeof(E) + 4) <= ELL_LDS_BYTES;
     if (ell && a.bi == 3 && a.bd == 3)
         launch_ell<E, 3, 3>(a, nnz_per_row, yrow, xrow, s);
     else if (a.bi == 3 && a.bd == 3)
-        launch_layouts<E, 3, 3>(a, yrow, xrow, blocks, s);
-    else if (a.bi == 12 && a.bd == 12) {
+        launch_generic<E, E, 3, 3>(a, yrow, xrow, s);
+    else if (a.bi == 12 && a.bd == 12)
         // one block row per wave: interleaving 2 or 4 rows per wave measured 6 % / 25 % slower
         // (more VGPRs, fewer waves to hide the HBM latency of the value stream)
-        if constexpr (std::is_same<E, double2>::value)
-            launch_bsr_mfma<double, true, 12, 12>(a, nnz_per_row, yrow, xrow, s);
-        else if constexpr (std::is_same<E, double>::value)
-            launch_bsr_mfma<double, false, 12, 12>(a, nnz_per_row, yrow, xrow, s);
-        else if constexpr (std::is_same<E, float2>::value)
-            launch_bsr_mfma<float, true, 12, 12>(a, nnz_per_row, yrow, xrow, s);
-        else
-            launch_bsr_mfma<float, false, 12, 12>(a, nnz_per_row, yrow, xrow, s);
-    }
+        launch_bsr_mfma<typename BsrMfmaScalar<E>::real, BsrMfmaScalar<E>::cplx, 12, 12>(a, nnz_per_row, yrow, xrow, s);
     // dense blocks from blk_min x blk_min on: bsr_blk_mfma_kernel where it was measured faster
     // than the generic kernel by more than the round-to-round spread (8^4 9-point operators,
     // complex<float> and complex<double>, profiles/bsr_blocks_measure.txt): 32x32 blocks and
@@ -2211,60 +1781,7 @@ void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipSt
     else if (blk_mfma_admits(a) && launch_blk<E>(a, yrow, xrow, s))
         return;
     else
-        launch_layouts<E, 0, 0>(a, yrow, xrow, blocks, s);
-}
-
-// The in-place adjoint, generic form (bsr.adj_inplace): bsr_kernel / bsr_mixed_kernel on the
-// transposed pattern with an entry indirection.  One thread per output element (block column J
-// of A, component c, rhs column); entry j of J reads block ent[j] of A's own value array -- the
-// same storage as the copy's block j, p.block_im_fast being the opposite of A's -- conjugated
-// (and widened to the vectors' type when the operator is the narrower one, both exact) at the
-// load.  Entries in list order (ascending nonzero index of A: the copy's order), the bd elements
-// ascending, Ops<>::fma on the same operands: the bits of the generic kernel on the conjugated
-// copy, and the same from run to run.  A block column with no entry writes alpha * 0 (plus y
-// when adding).  Every offset into v, x and y is 64-bit.
-template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
-    if constexpr (std::is_same<EX, EV>::value) return a;
-    else return widen(a);
-}
-
-template <typename EV, typename EX, bool YROW, bool XROW>
-__global__ void __launch_bounds__(256) bsr_adj_kernel(const BsrArgs p, const int *__restrict__ ent) {
-    const int bi = p.bi, bd = p.bd;
-    const long total = p.block_rows * bi * p.ncols;
-    const EV *__restrict__ v = (const EV *)p.v;
-    const EX *__restrict__ x = (const EX *)p.x;
-    EX *__restrict__ y = (EX *)p.y;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
-        long i, col;
-        int c;
-        if (YROW) {
-            col = idx % p.ncols;
-            const long t = idx / p.ncols;
-            c = (int)(t % bi);
-            i = t / bi;
-        } else {
-            c = (int)(idx % bi);
-            const long t = idx / bi;
-            i = t % p.block_rows;
-            col = t / p.block_rows;
-        }
-        EX acc = Ops<EX>::zero();
-        const int j0 = p.ii[i], j1 = p.ii[i + 1];
-        for (int j = j0; j < j1; ++j) {
-            const long d0 = p.jj[j];
-            const EV *vb = v + (long)ent[j] * bi * bd;
-            for (int e = 0; e < bd; ++e) {
-                const EX a = to_vec<EX>(Ops<EV>::conj(p.block_im_fast ? vb[c + (long)e * bi] : vb[(long)c * bd + e]));
-                const EX xv = XROW ? x[(d0 + e) * p.ldx + col] : x[(d0 + e) + col * p.ldx];
-                acc = Ops<EX>::fma(a, xv, acc);
-            }
-        }
-        const long img = i * bi + c;
-        EX *yp = YROW ? y + img * p.ldy + col : y + img + col * p.ldy;
-        const EX out = Ops<EX>::scale(acc, p.alpha_re, p.alpha_im);
-        *yp = p.add ? Ops<EX>::add(*yp, out) : out;
-    }
+        launch_generic<E, E, 0, 0>(a, yrow, xrow, s);
 }
 
 /// The in-place adjoint of a plain operator: the matrix-core form where launch_typed's
@@ -2277,24 +1794,9 @@ void launch_adj(const BsrArgs &a, const int *ent, bool yrow, bool xrow, hipStrea
             launch_blk<EX>(a, yrow, xrow, s, ent))
             return;
     }
-    const long total = a.block_rows * a.bi * a.ncols;
-    const long blocks = std::min((total + 255) / 256, 65536L);
     g_bsr_tune.last = 18;
-    KernelTimer timer("bsr", s);
-    if (yrow && xrow)
-        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, true, true>), dim3(blocks), dim3(256), 0, s, a, ent);
-    else if (yrow && !xrow)
-        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, true, false>), dim3(blocks), dim3(256), 0, s, a, ent);
-    else if (!yrow && xrow)
-        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, false, true>), dim3(blocks), dim3(256), 0, s, a, ent);
-    else
-        hipLaunchKernelGGL((bsr_adj_kernel<EV, EX, false, false>), dim3(blocks), dim3(256), 0, s, a, ent);
-    SBX_HIP_CHECK(hipGetLastError());
+    launch_generic<EV, EX, 0, 0, true>(a, yrow, xrow, s, ent);
 }
-
-template <typename E> __device__ __forceinline__ E conj_of(E v) { return v; }
-template <> __device__ __forceinline__ double2 conj_of<double2>(double2 v) { return double2{v.x, -v.y}; }
-template <> __device__ __forceinline__ float2 conj_of<float2>(float2 v) { return float2{v.x, -v.y}; }
 
 template <typename E>
 __global__ void __launch_bounds__(256) gather_blocks_kernel(const E *__restrict__ src,
@@ -2305,7 +1807,7 @@ __global__ void __launch_bounds__(256) gather_blocks_kernel(const E *__restrict_
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256L) {
         const long q = idx / be, e = idx - q * be;
         const E v = src[(long)perm[q] * be + e];
-        dst[idx] = conj ? conj_of<E>(v) : v;
+        dst[idx] = conj ? Ops<E>::conj(v) : v;
     }
 }
 

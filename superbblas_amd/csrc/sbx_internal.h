@@ -336,7 +336,7 @@ struct BsrTune {
     int mixed = 1; ///< single-precision operators applied to vectors of the double counterpart (float ->
                    ///< double, complex<float> -> complex<double>; the values are read in place and
                    ///< converted at the load, never copied): 1 = the blocks that blk_mfma / blk_min
-                   ///< admit go to bsr_blk_mfma_mixed_kernel where it was measured faster (blocks of
+                   ///< admit go to bsr_blk_mfma_kernel's mixed form where it was measured faster (blocks of
                    ///< 1024 elements and more at any column count, smaller ones from 4 rhs columns;
                    ///< blk_mfma 2: at any column count), 0 = every mixed product on the generic
                    ///< mixed kernel
@@ -361,9 +361,9 @@ struct BsrTune {
     /// (bsr_blk_mfma_kernel), 15 Kronecker adjoint, a thread per (domain site, column)
     /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element -- or, with
     /// last_mixed 1 (Kronecker operators are never mixed), dense blocks with single-precision
-    /// values and double-precision vectors on MFMA (bsr_blk_mfma_mixed_kernel),
-    /// 17 the in-place adjoint of dense blocks on MFMA (bsr_blk_mfma_adj_kernel), 18 the in-place
-    /// adjoint, a thread per output element (bsr_adj_kernel),
+    /// values and double-precision vectors on MFMA (bsr_blk_mfma_kernel, values narrower),
+    /// 17 the in-place adjoint of dense blocks on MFMA (bsr_blk_mfma_kernel, ADJ), 18 the in-place
+    /// adjoint, a thread per output element (bsr_kernel, ADJ),
     /// 0 another kernel
     std::atomic<int> last{0};
     /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type

@@ -1,7 +1,7 @@
 """A^H of plain BSR operators read from A's values in place ("bsr.adj_inplace" 1): bsr_krylov with
 the image labels on x reads the value array of create_bsr through an entry list, conjugating at
-the load -- bsr_blk_mfma_adj_kernel ("bsr.last_kernel" 17) where the dense-block clause would
-take the transposed copy, bsr_adj_kernel (18) otherwise -- so no second copy of the values exists
+the load -- bsr_blk_mfma_kernel's adjoint form ("bsr.last_kernel" 17) where the dense-block clause
+would take the transposed copy, bsr_kernel's (18) otherwise -- so no second copy of the values exists
 ("bsr.adj_copy_bytes") and A^H follows the changes the caller makes to them.  With the key at its
 default 0 nothing changes (the existing tests pin that; here only where a test needs both).
 

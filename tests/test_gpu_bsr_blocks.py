@@ -1,5 +1,5 @@
-"""bsr_blk_mfma_kernel (kernels_bsr.hip): dense blocks of 16 x 16 and more -- the multigrid
-coarse operators -- on the matrix cores, "bsr.last_kernel" 14.  Exact against the oracle's builtin
+"""bsr_blk_mfma_kernel (kernels_bsr.hip), its same-type form: dense blocks of 16 x 16 and more --
+the multigrid coarse operators -- on the matrix cores, "bsr.last_kernel" 14.  Exact against the oracle's builtin
 BSR loop (bsr.h:535-650) on integer-valued data: components are at most 6, a product component
 at most 61 and a row sum at most 9 * 128 * 61 = 70 272 < 2^24, so every sum is exact in float32
 in any order.  Small lattices: (2,2,2,2) has 16 rows of five blocks, (1,3,1,5) 15 rows of five

@@ -2,8 +2,8 @@
 complex<double> vectors (an extension of this library; the reference's bsr_krylov is one type
 throughout).  The values are read in place in their own type and widened at the load, products
 and sums are FP64: the result is the product of the up-converted operator with x.  Dense blocks
-of 16 x 16 and more run bsr_blk_mfma_mixed_kernel ("bsr.last_kernel" 16), everything else the
-generic mixed kernel (0); "bsr.last_mixed" reads 1 after either.
+of 16 x 16 and more run bsr_blk_mfma_kernel's mixed form ("bsr.last_kernel" 16), everything else
+the generic bsr_kernel's (0); "bsr.last_mixed" reads 1 after either.
 
 Exact against the oracle's builtin BSR loop in the double type on vals.astype(double type) (the
 conversion is exact) with integer-valued data: components are at most 6, a product component at

@@ -3,6 +3,9 @@
 
   gemm_isa_summary.py FILE.s          one line per kernel symbol
   gemm_isa_summary.py OLD.s NEW.s     the kernels whose lines differ (exit status 1 if any)
+  gemm_isa_summary.py OLD.s NEW.s RENAMES   the same, for kernels that changed their names: RENAMES
+                                      holds lines "old_symbol new_symbol", and a kernel of OLD.s
+                                      is compared with the kernel of NEW.s of its new name
 
 A line holds the instruction count, the counts of MFMA, other vector-ALU, scalar, branch, LDS,
 vector-memory and lane-move instructions (by opcode prefix alone) and the kernel descriptor's
@@ -52,7 +55,7 @@ def summarize(path):
 
 
 def main(argv):
-    if len(argv) not in (2, 3):
+    if len(argv) not in (2, 3, 4):
         sys.exit(__doc__)
     a = summarize(argv[1])
     if len(argv) == 2:
@@ -60,6 +63,9 @@ def main(argv):
             print(k, a[k])
         return 0
     b = summarize(argv[2])
+    if len(argv) == 4:
+        rename = dict(line.split() for line in open(argv[3]) if line.strip())
+        a = {rename.get(k, k): v for k, v in a.items()}
     diff = [k for k in sorted(set(a) | set(b)) if a.get(k) != b.get(k)]
     for k in diff:
         print("%s\n  - %s\n  + %s" % (k, a.get(k, "(absent)"), b.get(k, "(absent)")))

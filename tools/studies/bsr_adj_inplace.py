@@ -7,7 +7,8 @@ sides (1, 4, 12, 16), x pxyztscn (row major) -> y pXYZTSCn, random values -- two
            ("bsr.last_kernel" 17 / 18)
   copy     A^H through the conjugated, regrouped copy, in the library of the tree BASE (the build
            of the commit before the in-place adjoint: the baseline is not the code under study;
-           BASE unset: this tree with the key at 0)
+           BASE unset: this tree with the key at 0; BASE_KEY=1: BASE's library with the key at 1
+           too, its in-place kernels against this tree's, the "copy" columns then hold BASE's)
 Each way runs in a worker process of its own (two libraries cannot share a process); the driver
 hands out the rounds in turn, so the rounds of the two ways alternate, both processes warm:
 ROUNDS rounds (at least 3) after one warm-up round, every figure the library's HIP-event time of
@@ -118,7 +119,8 @@ def driver():
     rounds = max(3, int(os.environ.get("ROUNDS", "3")))
     ns = [int(v) for v in env_list("N", "1,4,12,16")]
     base = os.environ.get("BASE")
-    ways = {"inplace": ("1", ROOT), "copy": ("0", base or ROOT)}
+    # BASE_KEY 1: BASE reads in place too (this tree's in-place kernels against another build's)
+    ways = {"inplace": ("1", ROOT), "copy": (os.environ.get("BASE_KEY", "0"), base or ROOT)}
     procs = {}
     for way, (flag, root) in ways.items():
         env = dict(os.environ, SB_ROOT=root)

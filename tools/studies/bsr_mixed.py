@@ -7,7 +7,7 @@ type.  Four forms per point, alternating over ROUNDS rounds (at least 3, after o
 in one warm process; every figure is the library's HIP-event time of the "bsr" kernels over REPS
 calls:
   a  mixed, matrix cores: complex<float> operator, complex<double> vectors, "bsr.mixed" 1 with
-     "bsr.blk_mfma" 2 (bsr_blk_mfma_mixed_kernel at any column count)
+     "bsr.blk_mfma" 2 (bsr_blk_mfma_kernel's mixed form at any column count)
   b  mixed, generic: "bsr.mixed" 0
   c  the same values as a complex<double> operator, complex<double> vectors, default dispatch
      (what a caller has to do without the mixed product)
