@@ -103,6 +103,20 @@ inline Context createCudaContext(int) {
 
 struct BSR_handle; // opaque (sbx_bsr)
 
+/// Half-precision value types of create_bsr (an extension): IEEE binary16 and a complex of two
+/// of them (re, im).  Storage only -- the bit patterns, trivially copyable, the layout of
+/// _Float16 / __half / __half2 and of torch's float16 / complex32 -- with no arithmetic: the
+/// library never computes in 16 bits on the host, and the header needs no compiler support for
+/// the format.  Fill them from the bits of a conversion of your own (or from _Float16 where the
+/// compiler has it: create_bsr<Nd, Ni, _Float16> maps to the same type).
+struct float16 {
+    std::uint16_t bits;
+};
+struct complex_float16 {
+    float16 re, im;
+};
+static_assert(sizeof(float16) == 2 && sizeof(complex_float16) == 4, "binary16 layout");
+
 /// supported_type<T>::value: whether T is an element type of the library (platform.h:686-712,
 /// 818-821)
 template <typename T> struct supported_type { static constexpr bool value = false; };
@@ -242,6 +256,12 @@ template <> struct dtype<std::complex<float>> { static constexpr int value = SBX
 template <> struct dtype<std::complex<double>> { static constexpr int value = SBX_CDOUBLE; };
 template <> struct dtype<int> { static constexpr int value = SBX_INT; };
 template <> struct dtype<std::size_t> { static constexpr int value = SBX_SIZE_T; };
+/// The half-precision value types of create_bsr (below); every other call refuses them
+template <> struct dtype<float16> { static constexpr int value = SBX_HALF; };
+template <> struct dtype<complex_float16> { static constexpr int value = SBX_CHALF; };
+#ifdef __FLT16_MANT_DIG__
+template <> struct dtype<_Float16> { static constexpr int value = SBX_HALF; };
+#endif
 /// char has no values type in the C ABI (the reference's own char save / load do not compile,
 /// tensor.h:1091, no multiplication_cost<char>): -1 fails every library call on char tensors
 /// loudly, while programs that only name the type (tests/storage_details.cpp's type switch over a
@@ -613,6 +633,12 @@ void contraction(T alpha, const PartitionItem<Nd0> *p0, const Coor<Nd0> &from0,
 /// the caller's array, no converted copy is kept -- and products, sums, alpha, beta and y are
 /// double: the result is the product of the up-converted operator with x.  Every other pair of
 /// types, and any type difference on an operator of create_kron_bsr, throws as before.
+/// The same one step down: an operator of create_bsr<Nd, Ni, float16> or
+/// <Nd, Ni, complex_float16> (IEEE binary16 values, above) is contracted by bsr_krylov with T =
+/// float / std::complex<float>; the values are widened to float exactly where they are read, and
+/// products, sums, alpha, beta and y are float.  binary16 holds magnitudes up to 65504 (smallest
+/// subnormal 2^-24): scale the operator into range and pass the scale in alpha.  Half operators
+/// with double vectors and create_kron_bsr with half values throw.
 ///
 /// The image side (x with the image labels, y = alpha A^H x) of a create_bsr operator: by default
 /// the first such product makes a conjugated, regrouped copy of the value blocks that all later

@@ -35,7 +35,10 @@ extern "C" {
 #define SBX_ERROR (-1)
 
 /* Scalar types (reference supported_type, blas.h:57-65 / performance.h:29-48) */
-enum sbx_dtype { SBX_FLOAT = 0, SBX_DOUBLE = 1, SBX_CFLOAT = 2, SBX_CDOUBLE = 3, SBX_INT = 4, SBX_SIZE_T = 5 };
+enum sbx_dtype { SBX_FLOAT = 0, SBX_DOUBLE = 1, SBX_CFLOAT = 2, SBX_CDOUBLE = 3, SBX_INT = 4, SBX_SIZE_T = 5,
+                 /* IEEE binary16 and a complex of two of them (re, im): the type of the values v of
+                    sbx_create_bsr only (see there); every tensor argument refuses them */
+                 SBX_HALF = 6, SBX_CHALF = 7 };
 /* CoorOrder (tensor.h:56-60) */
 enum sbx_coor_order { SBX_SLOW_TO_FAST = 0, SBX_FAST_TO_SLOW = 1 };
 /* CopyAdd (tensor.h:62-66) */
@@ -122,7 +125,9 @@ int sbx_timings_report(char *buf, int len);
    kernel bsr_blk_mfma_kernel: 1, the default, where it was measured faster than the generic kernel -- blocks
    of 1024 elements and more at any rhs column count, of 576 and more from 4 columns, smaller ones from 12;
    2 at any column count; 0 the generic kernel; 3x3, 12x12 and Kronecker operators keep their kernels),
-   "bsr.mixed" (a float / complex<float> operator applied to double / complex<double> vectors, see
+   "bsr.mixed" (a float / complex<float> operator applied to double / complex<double> vectors, or an
+   SBX_HALF / SBX_CHALF operator applied to float / complex<float> vectors -- for these, blocks of more than 256
+   and fewer than 1024 elements from 12 columns, the rest as follows --, see
    sbx_bsr_krylov: 1, the default, the dense blocks that "bsr.blk_mfma", "bsr.blk_min" and "bsr.variant" admit
    on the matrix-core kernel bsr_blk_mfma_kernel (its mixed form) where it was measured faster than the generic
    kernel's mixed form -- blocks of 1024 elements and more at any rhs column count, smaller ones from 4 columns;
@@ -142,7 +147,7 @@ int sbx_timings_report(char *buf, int len);
    bsr_kernel's adjoint form, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
    by the value copies of transposed operators, process-wide: it grows when a copy is made and shrinks when
    its operator is destroyed; it cannot be set), "bsr.last_mixed" (1 when the last BSR
-   launch read values of a narrower type than its vectors, else 0), "dist.peer_copies",
+   launch read values of a narrower type than its vectors -- float under double, half under float --, else 0), "dist.peer_copies",
    "copy.last_pair", "gemm.last_herm" (tiles per batch entry the last GEMM launch mirrored instead
    of computed; 0 = a full product), "gemm.last_lean" (1 when the last GEMM launch took the lean form of
    the complex<double> 128x128x16 kernel, key "gemm.lean", on by default and bit-identical to the generic
@@ -271,7 +276,11 @@ int sbx_contraction(int nd0, int nd1, int ndr, int t, const double *alpha,
    2554-2580 bsr_get_preferred_layout) ----
    ii[c]: number of nonzero blocks of each block row of component c (not a prefix sum);
    jj[c]: nd ints per nonzero block, the domain coordinate of the block relative to the domain
-   partition's `from` (a -1 first coordinate skips the block, ELL form). */
+   partition's `from` (a -1 first coordinate skips the block, ELL form).
+   t, the type of the values v: SBX_FLOAT, SBX_DOUBLE, SBX_CFLOAT, SBX_CDOUBLE or -- here only,
+   an extension -- SBX_HALF / SBX_CHALF: IEEE binary16 values (2 bytes; re, im: 4 bytes) of an
+   operator that sbx_bsr_krylov applies to SBX_FLOAT / SBX_CFLOAT vectors (see there).  Host
+   (CPU-context) components are mirrored to the device byte for byte in every type. */
 int sbx_create_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const int *pdm,
                    const int *dimd, int ncomponents, const int *blockim, const int *blockdm,
                    int blockImFast, const int *const *ii, const int *const *jj,
@@ -287,7 +296,8 @@ int sbx_create_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const
    work, as for sbx_create_bsr: with the image labels on x, sbx_bsr_krylov computes
    y = alpha A^H x (beyond the reference, whose local Kronecker operators throw "unsupported
    conjugation", bsr.h:399, 1032); A^H reads v and kronv in place, conj-transposed, so it follows
-   changes made to them just as A does. */
+   changes made to them just as A does.  t is one of the four floating-point tensor types:
+   SBX_HALF / SBX_CHALF fail with "unsupported type". */
 int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const int *pdm,
                         const int *dimd, int ncomponents, const int *blockim, const int *blockdm,
                         const int *kronim, const int *krondm, int blockImFast,
@@ -305,8 +315,13 @@ int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, 
    with x, at half the operator's memory and value traffic.  No converted copy is made: values
    changed after one product show in the next.  Both contraction sides (A^H through the
    transposed operator, which stays in the operator's type), any layout and partition,
-   temporaries, powers, just_local, requests and host contexts work as for one type.  Every other
-   difference of types fails with the same errors as before and leaves y untouched. */
+   temporaries, powers, just_local, requests and host contexts work as for one type.
+   The same one step down: t = SBX_FLOAT for an SBX_HALF operator and SBX_CFLOAT for an SBX_CHALF
+   one.  The binary16 values are converted to float exactly (subnormals included) where they are
+   loaded; products, sums, alpha, beta and y are float.  binary16 holds magnitudes up to 65504
+   (smallest subnormal 2^-24): scale the operator into range and pass the scale in alpha.
+   Every other difference of types -- a half operator with double or half vectors among them --
+   fails with the same errors as before and leaves y untouched. */
 int sbx_bsr_krylov(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, const double *alpha,
                    const char *oim, const char *odm, const int *px, int ncomponents,
                    const char *ox, const int *fromx, const int *sizex, const int *dimx,

@@ -39,6 +39,9 @@ Copy, Add = 0, 1
 RowMajor, ColumnMajor = 0, 1
 CPU, GPU = 0, 1
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT, SIZE_T = range(6)
+# IEEE binary16 and a complex of two (re, im): the values of create_bsr only (a half-precision
+# operator applied to single-precision vectors); every other call refuses them
+HALF, CHALF = 6, 7
 
 _DTYPES = {
     torch.float32: FLOAT,
@@ -48,6 +51,8 @@ _DTYPES = {
     torch.int32: INT,
     torch.int64: SIZE_T,
     torch.uint64: SIZE_T,
+    torch.float16: HALF,
+    torch.complex32: CHALF,
 }
 
 

@@ -404,7 +404,7 @@ BsrOp *bsr_create(int nd, int ni, int dtype, const std::vector<std::vector<Range
             SBX_HIP_CHECK(hipMemcpy(hjj_coor.data(), jj[c], sizeof(int) * nnz * nd,
                                     hipMemcpyDefault));
         if (host) {
-            const std::size_t es = dtype_size(dtype);
+            const std::size_t es = bsr_value_size(dtype);
             const std::size_t vbytes = es * (std::size_t)nnz * bi * bd;
             SBX_HIP_CHECK(hipMalloc(&bc.owned_v, std::max<std::size_t>(vbytes, 1)));
             if (vbytes) SBX_HIP_CHECK(hipMemcpy(bc.owned_v, v[c], vbytes, hipMemcpyHostToDevice));
@@ -616,7 +616,7 @@ BsrOp *make_transposed(const BsrOp &a) {
 /// never allocates the copy.
 void adjoint_values(const BsrOp &a, BsrOp &t, bool inplace) {
     const long be = volume(a.blocki) * volume(a.blockd);
-    const std::size_t es = dtype_size(a.dtype);
+    const std::size_t es = bsr_value_size(a.dtype);
     for (BsrComp &bc : t.comps) {
         if (bc.block_rows == 0 || (inplace ? bc.adj_ent != nullptr : bc.owned_v != nullptr)) continue;
         const long nnz = (long)bc.adj_perm.size();
@@ -805,11 +805,13 @@ void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const s
             (op.kroni[i] > 1 && op.kroni[i] != op.dimi[i]))
             throw Error("Still not supported partially blocking a dimension");
     // x and y have the operator's type, or -- an extension, not for Kronecker operators -- a
-    // single-precision operator is applied to vectors of its double counterpart: the values are
-    // read in place and widened at the load, everything else (temporaries, halo exchange,
-    // copies) is in x's type
+    // single-precision operator is applied to vectors of its double counterpart, or a
+    // half-precision one to vectors of its single counterpart: the values are read in place and
+    // widened at the load, everything else (temporaries, halo exchange, copies) is in x's type
     const bool mixed = !op.is_kron && ((op.dtype == SBX_FLOAT && x.dtype == SBX_DOUBLE) ||
-                                       (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE));
+                                       (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE) ||
+                                       (op.dtype == SBX_HALF && x.dtype == SBX_FLOAT) ||
+                                       (op.dtype == SBX_CHALF && x.dtype == SBX_CFLOAT));
     if (x.dtype != y.dtype || (x.dtype != op.dtype && !mixed))
         throw Error("bsr_krylov: type mismatch");
     const int dtype = x.dtype;

@@ -217,6 +217,8 @@ void attach_masks(DistTensor &t, const float *const *mask, int ncomponents,
 void check_copy_types(int t0, int t1) {
     auto real = [](int t) { return t == SBX_FLOAT || t == SBX_DOUBLE; };
     auto index = [](int t) { return t == SBX_INT || t == SBX_SIZE_T; };
+    // (the half-precision types are operator values only: no tensor has them)
+    if (dtype_is_half(t0) || dtype_is_half(t1)) throw Error("copy: unsupported type");
     if (t0 == t1 || (real(t0) && (real(t1) || dtype_is_complex(t1))) ||
         (dtype_is_complex(t0) && dtype_is_complex(t1)) || (index(t0) && index(t1)))
         return;
@@ -1021,6 +1023,8 @@ int create_bsr_any(int nd, int ni, int t, const int *pim, const int *dimi, const
     return guard([&] {
         check_session(session);
         if (!bsrh) throw Error("create_bsr: null handle output");
+        // the half-precision value types: operators of sbx_create_bsr only
+        if (kronv && dtype_is_half(t)) throw Error("create_kron_bsr: unsupported type");
         const Comm c = get_comm(comm);
         const bool rev = co == SBX_FAST_TO_SLOW;
         std::vector<const int *> vii, vjj;
@@ -1096,9 +1100,12 @@ int sbx_bsr_krylov_req(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, cons
         check_session(session);
         if (!bsrh || !bsrh->op) throw Error("bsr_krylov: invalid handle");
         // T is the operator's type, or (not for Kronecker operators) the double counterpart of a
-        // single-precision operator: the mixed product of bsr.cpp
+        // single-precision operator or the single counterpart of a half-precision one: the mixed
+        // products of bsr.cpp
         const bool mixed = !bsrh->is_kron && ((bsrh->dtype == SBX_FLOAT && t == SBX_DOUBLE) ||
-                                              (bsrh->dtype == SBX_CFLOAT && t == SBX_CDOUBLE));
+                                              (bsrh->dtype == SBX_CFLOAT && t == SBX_CDOUBLE) ||
+                                              (bsrh->dtype == SBX_HALF && t == SBX_FLOAT) ||
+                                              (bsrh->dtype == SBX_CHALF && t == SBX_CFLOAT));
         if (bsrh->nd != nd || bsrh->ni != ni || (bsrh->dtype != t && !mixed))
             throw Error("Given BSR handle doesn't match the template parameters Nd, Ni, or T");
         if (co != bsrh->co)

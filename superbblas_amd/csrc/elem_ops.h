@@ -55,6 +55,25 @@ template <> struct Ops<float> {
     static __device__ __forceinline__ bool nonzero(float a) { return a != 0; }
 };
 
+// IEEE binary16 (f16) and a complex of two of them (f16x2: re, im), the types of BSR operator
+// values kept in half precision.  Storage only: a value is widened to float / float2 where it is
+// loaded (v_cvt_f32_f16: exact, subnormals included) and no arithmetic is done in 16 bits; the
+// conjugation is the sign-bit flip of the imaginary part (exact on every bit pattern).
+typedef _Float16 f16;
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+template <> struct Ops<f16> {
+    static __device__ __forceinline__ f16 conj(f16 a) { return a; }
+};
+template <> struct Ops<f16x2> {
+    static __device__ __forceinline__ f16x2 conj(f16x2 a) {
+        unsigned u;
+        __builtin_memcpy(&u, &a, 4);
+        u ^= 0x80000000u;
+        __builtin_memcpy(&a, &u, 4);
+        return a;
+    }
+};
+
 /// Non-temporal (streaming) store of one element: the line is written through without being
 /// kept in the caches (outputs written once and not re-read by the same kernel)
 template <typename D> __device__ __forceinline__ void store_nt(D *p, D v) {

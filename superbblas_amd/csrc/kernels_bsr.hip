@@ -47,9 +47,12 @@ struct BsrArgs {
 };
 
 // A value of the operator's type EV as the vectors' type EX: itself, or an operator kept in
-// single precision (float, float2) widened to the double counterpart (exact)
+// single precision (float, float2) widened to the double counterpart, or one kept in half
+// precision (f16, f16x2) widened to the single counterpart (both exact)
 __device__ __forceinline__ double widen(float a) { return (double)a; }
 __device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
+__device__ __forceinline__ float widen(f16 a) { return (float)a; }
+__device__ __forceinline__ float2 widen(f16x2 a) { return float2{(float)a.x, (float)a.y}; }
 template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
     if constexpr (std::is_same<EX, EV>::value) return a;
     else return widen(a);
@@ -58,9 +61,10 @@ template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
 // The generic form, any block size, pattern and layout: one thread per output element, for
 //  * same-type products (EV == EX; BI_, BD_ > 0: a compile-time block shape);
 //  * mixed products: an operator kept in single precision (EV: float, float2) applied to vectors
-//    of the double counterpart (EX).  The values are read in place as EV and widened at the load
-//    (exact); products, sums, alpha and the store of y are FP64.  No converted copy of the
-//    values exists;
+//    of the double counterpart (EX), or one kept in half precision (EV: f16, f16x2) applied to
+//    vectors of the single counterpart.  The values are read in place as EV and widened at the
+//    load (exact); products, sums, alpha and the store of y are in EX's precision.  No converted
+//    copy of the values exists;
 //  * ADJ, the in-place adjoint (bsr.adj_inplace): the transposed pattern with an entry
 //    indirection.  The output element is (block column J of A, component c, rhs column); entry j
 //    of J reads block ent[j] of A's own value array -- the same storage as the copy's block j,
@@ -292,10 +296,13 @@ template <> struct BsrMfmaElem<double, true> { typedef double2 type; };
 template <> struct BsrMfmaElem<double, false> { typedef double type; };
 template <> struct BsrMfmaElem<float, true> { typedef float2 type; };
 template <> struct BsrMfmaElem<float, false> { typedef float type; };
+template <> struct BsrMfmaElem<f16, true> { typedef f16x2 type; }; // (operator values only)
+template <> struct BsrMfmaElem<f16, false> { typedef f16 type; };
 // BsrMfmaElem's inverse: the real type and the complexity of an element type
 template <typename E> struct BsrMfmaScalar { typedef E real; static constexpr bool cplx = false; };
 template <> struct BsrMfmaScalar<double2> { typedef double real; static constexpr bool cplx = true; };
 template <> struct BsrMfmaScalar<float2> { typedef float real; static constexpr bool cplx = true; };
+template <> struct BsrMfmaScalar<f16x2> { typedef f16 real; static constexpr bool cplx = true; };
 // 16x16x4 MFMA per real type and its C/D row map (col = lane & 15)
 template <typename R> struct BsrMfma;
 template <> struct BsrMfma<double> {
@@ -1461,6 +1468,17 @@ void launch_ell(const BsrArgs &a, int nnz, bool yrow, bool xrow, hipStream_t s) 
 //    every read.  So the H pieces of a group lie XW slots apart, image [k-group][piece][column]:
 //    the slot of a read is c mod 16, every lane group covers the 16 slots once, no conflict.
 //    (For either pair that is the same-type image of the double type; H = 1 gives form 14's.)
+//    The same form with RV = f16, R = float: an operator kept in half precision applied to
+//    single-precision vectors on v_mfma_f32_16x16x4_f32.  A lane's 16-byte value load is VA = 4
+//    complex-half or 8 half consecutive k, widened (exact: v_cvt_f32_f16) in registers; x is
+//    staged as float2 / float, VE = 2 / 4, so again H = VA / VE = 2 and a k-step is 4 VA = 16
+//    (complex) or 32 (real) k -- kpad, kparts and the ragged tails follow from VA alone.  The
+//    bank argument above counts 16-byte slots and never the element size: a piece is one slot
+//    whether it holds 1 double2, 2 float2 or 4 float, element k of column c lies in slot
+//    (k / VE) XW + c = ((k / VA) H + (k % VA) / VE) XW + c, XW is a multiple of 16, and so the
+//    slot of lane (c, kq)'s read h is c mod 16 for 8- and 4-byte elements too: every 16-lane
+//    group of a ds_read_b128 covers the 16 slots of the bank row once.  (The staging stores are
+//    form 14's for float2 / float, one element each.)
 //  * 17, ADJ, the in-place adjoint (bsr.adj_inplace): the transposed operator's pattern over A's
 //    own value array.  Entry j of a block row reads block ent[j] of A instead of block j of the
 //    copy, and the imaginary parts are negated in registers as a fragment is loaded (real types
@@ -1676,8 +1694,8 @@ __global__ void __launch_bounds__(512) bsr_blk_mfma_kernel(const BsrArgs p, cons
 }
 
 /// false: not this shape (the generic kernel runs).  Values RV, vectors R (the same, or float
-/// values and double vectors: form 16).  Limits, by the vector type: bi <= 128 (8 strips, one wave
-/// each), two x buffers of kpad x 16 columns within 64 KB of LDS (kpad: bd rounded up to 4 VA; bd
+/// values and double vectors, or half values and float vectors: form 16).  Limits, by the
+/// vector type: bi <= 128 (8 strips, one wave each), two x buffers of kpad x 16 columns within 64 KB of LDS (kpad: bd rounded up to 4 VA; bd
 /// <= 128 for complex<double>, 256 for 8-byte and 512 for 4-byte vector elements), NT reduced to
 /// stay within 32 KB where possible, at most 65535 groups of NT column tiles.
 /// ent: the in-place adjoint (form 17; same-type products), under the same limits.
@@ -1740,13 +1758,23 @@ bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int
 /// profiles/bsr_mixed_measure.txt): 32x32 blocks and larger at any column count (1.25-5.8x), 16x16
 /// and 24x24 from 4 columns (1.04x / 1.02x at 4, 2.6-4.0x from 12; at one column 0.73x / 0.89x);
 /// between the measured sizes the bound goes by the block's elements: 1024 and more at any column
-/// count, fewer from 4 columns (float -> double: the same bound, not measured).  blk_mfma 2: no
-/// column bound.  3x3 and 12x12 blocks and everything else run the generic mixed form.
+/// count, fewer from 4 columns (float -> double: the same bound, not measured).
+/// Half-precision operators with single-precision vectors, measured the same way (complex32
+/// values, complex<float> vectors, profiles/bsr_half_measure.txt): 32x32 blocks and larger at any
+/// column count (1.66-8.6x), 16x16 from 4 columns (1.38x at 4, 3.3-4.3x from 12; at one column
+/// 0.93x), 24x24 from 12 columns (2.3-3.9x; 0.79x / 0.87x at 1 / 4 columns: its rows are padded to
+/// the k-step of 16, the work of a 32x32 block); between the measured sizes by the block's
+/// elements, more than 256 and fewer than 1024 from 12 columns (float16 -> float: the same
+/// bound, carried over, not measured).
+/// blk_mfma 2: no column bound.  3x3 and 12x12 blocks and everything else run the generic mixed
+/// form.
 template <typename EV, typename EX>
 void launch_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+    constexpr bool HALF = std::is_same<EV, f16>::value || std::is_same<EV, f16x2>::value;
+    const long be = (long)a.bi * a.bd;
+    const int min_cols = g_bsr_tune.blk_mfma >= 2 || be >= 32 * 32 ? 1 : HALF && be > 16 * 16 ? 12 : 4;
     if (g_bsr_tune.mixed && g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
-        a.bd >= g_bsr_tune.blk_min &&
-        a.ncols >= (g_bsr_tune.blk_mfma >= 2 || a.bi * a.bd >= 32 * 32 ? 1 : 4) &&
+        a.bd >= g_bsr_tune.blk_min && a.ncols >= min_cols &&
         launch_blk<EV, EX>(a, yrow, xrow, s))
         return;
     launch_generic<EV, EX, 0, 0>(a, yrow, xrow, s);
@@ -1832,6 +1860,9 @@ void launch_gather_blocks(int t, const void *src, const int *perm, long nblocks,
     case SBX_CFLOAT: return gather_typed<float2>(src, perm, nblocks, block_elems, conj_values, dst, s);
     case SBX_DOUBLE: return gather_typed<double>(src, perm, nblocks, block_elems, false, dst, s);
     case SBX_FLOAT: return gather_typed<float>(src, perm, nblocks, block_elems, false, dst, s);
+    // half-precision operators: the copy stays in the operator's type (conjugation: a sign bit)
+    case SBX_CHALF: return gather_typed<f16x2>(src, perm, nblocks, block_elems, conj_values, dst, s);
+    case SBX_HALF: return gather_typed<f16>(src, perm, nblocks, block_elems, false, dst, s);
     default: throw Error("bsr: unsupported type");
     }
 }
@@ -1867,6 +1898,8 @@ void launch_bsr(const BsrDesc &d, int device) {
         const bool yr = d.y_row_major, xr = d.x_row_major;
         if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_adj<float2, double2>(a, d.adj_ent, yr, xr, s);
         if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_adj<float, double>(a, d.adj_ent, yr, xr, s);
+        if (d.tv == SBX_CHALF && d.t == SBX_CFLOAT) return launch_adj<f16x2, float2>(a, d.adj_ent, yr, xr, s);
+        if (d.tv == SBX_HALF && d.t == SBX_FLOAT) return launch_adj<f16, float>(a, d.adj_ent, yr, xr, s);
         if (d.tv != d.t) throw Error("bsr: unsupported pair of value and vector types");
         switch (d.t) {
         case SBX_CDOUBLE: return launch_adj<double2, double2>(a, d.adj_ent, yr, xr, s);
@@ -1877,11 +1910,16 @@ void launch_bsr(const BsrDesc &d, int device) {
         }
     }
     if (d.tv != d.t) {
-        // single-precision values, double-precision vectors (bsr_krylov admits these two pairs)
+        // single-precision values with double-precision vectors, half-precision values with
+        // single-precision vectors (bsr_krylov admits these four pairs)
         if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE)
             return launch_mixed<float2, double2>(a, d.y_row_major, d.x_row_major, s);
         if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE)
             return launch_mixed<float, double>(a, d.y_row_major, d.x_row_major, s);
+        if (d.tv == SBX_CHALF && d.t == SBX_CFLOAT)
+            return launch_mixed<f16x2, float2>(a, d.y_row_major, d.x_row_major, s);
+        if (d.tv == SBX_HALF && d.t == SBX_FLOAT)
+            return launch_mixed<f16, float>(a, d.y_row_major, d.x_row_major, s);
         throw Error("bsr: unsupported pair of value and vector types");
     }
     switch (d.t) {

@@ -48,6 +48,16 @@ inline std::size_t dtype_size(int t) {
     }
 }
 inline bool dtype_is_complex(int t) { return t == SBX_CFLOAT || t == SBX_CDOUBLE; }
+/// Size in bytes of a value of a BSR operator: a tensor's scalar types and, for operators of
+/// sbx_create_bsr only, the half-precision types that no tensor has (dtype_size refuses them)
+inline std::size_t bsr_value_size(int t) {
+    switch (t) {
+    case SBX_HALF: return 2;
+    case SBX_CHALF: return 4;
+    default: return dtype_size(t);
+    }
+}
+inline bool dtype_is_half(int t) { return t == SBX_HALF || t == SBX_CHALF; }
 
 /// A complex scalar carried through the host planner (alpha/beta)
 struct Scalar {
