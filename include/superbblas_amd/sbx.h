@@ -132,6 +132,11 @@ int sbx_timings_report(char *buf, int len);
    on the matrix-core kernel bsr_blk_mfma_kernel (its mixed form) where it was measured faster than the generic
    kernel's mixed form -- blocks of 1024 elements and more at any rhs column count, smaller ones from 4 columns;
    "bsr.blk_mfma" 2 at any column count; 0 every mixed product on the generic mixed kernel; never a converted copy),
+   "bsr.mixed12_min_cols" (mixed products of 12x12 blocks, all four pairs: from this many rhs columns on -- default 4,
+   1 = at any column count -- the 12x12 matrix-core kernels with the values read in their own type and widened at
+   the load, chosen by "bsr.variant", "bsr.blk_pd" and the x layout as for same-type products; fewer columns, and
+   "bsr.mixed" 0, the generic mixed kernel), "bsr.mixed12_pack" (the ring slots of their LDS-DMA form: 1, the
+   default, packed below 12 columns, 0 never, 2 always),
    "bsr.adj_inplace" (A^H products, x with the image labels, of operators of sbx_create_bsr; read at each
    product: 0, the default, through a conjugated, regrouped copy of the value blocks made at the first such
    product -- a snapshot of the values, and as many bytes again; 1 from A's own value array in place through a
@@ -143,7 +148,8 @@ int sbx_timings_report(char *buf, int len);
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
    last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel; 16 with "bsr.last_mixed" 1 =
-   its mixed form, 0 with it = the generic kernel bsr_kernel's mixed form; 17 = bsr_blk_mfma_kernel's and 18 =
+   its mixed form, 0 with it = the generic kernel bsr_kernel's mixed form, 7 / 8 / 10 / 11 with it = the 12x12
+   matrix-core kernels reading the narrower values; 17 = bsr_blk_mfma_kernel's and 18 =
    bsr_kernel's adjoint form, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
    by the value copies of transposed operators, process-wide: it grows when a copy is made and shrinks when
    its operator is destroyed; it cannot be set), "bsr.last_mixed" (1 when the last BSR

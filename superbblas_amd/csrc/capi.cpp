@@ -458,6 +458,8 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "bsr.blk_mfma") g_bsr_tune.blk_mfma = (int)value;
         else if (k == "bsr.blk_min") g_bsr_tune.blk_min = (int)value;
         else if (k == "bsr.mixed") g_bsr_tune.mixed = (int)value;
+        else if (k == "bsr.mixed12_min_cols") g_bsr_tune.mixed12_min_cols = (long)value;
+        else if (k == "bsr.mixed12_pack") g_bsr_tune.mixed12_pack = (int)value;
         else if (k == "bsr.adj_inplace") g_bsr_tune.adj_inplace = (int)value;
         else if (k == "bsr.adj_copy_bytes") throw Error("tune_set: bsr.adj_copy_bytes is read-only");
         else if (k == "bsr.tile") g_bsr_tune.tile = (int)value;
@@ -539,6 +541,8 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "bsr.tile") *value = g_bsr_tune.tile;
         else if (k == "bsr.tile_min_cols") *value = g_bsr_tune.tile_min_cols;
         else if (k == "bsr.mixed") *value = g_bsr_tune.mixed;
+        else if (k == "bsr.mixed12_min_cols") *value = g_bsr_tune.mixed12_min_cols;
+        else if (k == "bsr.mixed12_pack") *value = g_bsr_tune.mixed12_pack;
         else if (k == "bsr.last_kernel") *value = g_bsr_tune.last;
         else if (k == "bsr.last_mixed") *value = g_bsr_tune.last_mixed;
         else if (k == "bsr.adj_inplace") *value = g_bsr_tune.adj_inplace;

@@ -291,6 +291,16 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned off, u
                      : "memory", "m0");
 }
 
+/// An element of a narrower operator as it lies in memory (EV), read as the vectors' type EX: the
+/// load widens.  A same-type kernel's stored type is EX itself, so its loads are the plain ones
+/// (the 12x12 same-type kernels compile as before, profiles/bsr_mixed12_isa.txt).
+template <typename EV, typename EX> struct BsrNarrow {
+    EV val;
+    __device__ __forceinline__ operator EX() const { return widen(val); }
+};
+template <typename EV, typename EX> struct BsrStored { typedef BsrNarrow<EV, EX> type; };
+template <typename EX> struct BsrStored<EX, EX> { typedef EX type; };
+
 template <typename R, bool CPLX> struct BsrMfmaElem;
 template <> struct BsrMfmaElem<double, true> { typedef double2 type; };
 template <> struct BsrMfmaElem<double, false> { typedef double type; };
@@ -323,13 +333,14 @@ template <> struct BsrMfma<float> {
 // One block row per wave, the fragments of nonzero block t+1 loaded while block t is applied
 // (twice the bytes in flight per wave; 985 -> 880 us on the chain's complex<float> operator).
 // Mapping consecutive block rows to one XCD was measured no faster.
-template <typename R, bool CPLX, int BI, int BD, bool YROW, bool XROW>
+template <typename RV, typename R, bool CPLX, int BI, int BD, bool YROW, bool XROW>
 __global__ void __launch_bounds__(256) bsr_mfma_pf_kernel(const BsrArgs p, long ntiles_n) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    typedef typename BsrMfmaElem<R, CPLX>::type E; // the vectors; the values as stored, widening at the load:
+    typedef typename BsrStored<typename BsrMfmaElem<RV, CPLX>::type, E>::type EV;
     typedef typename BsrMfma<R>::acc_t acc_t;
     static_assert(BI <= 16 && BD % 4 == 0, "block shape");
     constexpr int KS = BD / 4;
-    const E *__restrict__ v = (const E *)p.v;
+    const EV *__restrict__ v = (const EV *)p.v;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const int lane = threadIdx.x & 63;
@@ -350,7 +361,7 @@ __global__ void __launch_bounds__(256) bsr_mfma_pf_kernel(const BsrArgs p, long 
         const int dj = p.jj[j];
         const bool ok = dj >= 0;
         const long d0 = ok ? dj : 0;
-        const E *vb = v + (long)j * BI * BD;
+        const EV *vb = v + (long)j * BI * BD;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int e = ks * 4 + kq;
@@ -400,13 +411,14 @@ __global__ void __launch_bounds__(256) bsr_mfma_pf_kernel(const BsrArgs p, long 
 // row's block columns are read first (scalar loads), then the fragments of NB blocks at a time
 // are loaded one group ahead of the MFMAs, so no load waits on another load and NB blocks' bytes
 // are in flight per wave.
-template <typename R, bool CPLX, int BI, int BD, bool YROW, bool XROW, int NNZ, int NB>
+template <typename RV, typename R, bool CPLX, int BI, int BD, bool YROW, bool XROW, int NNZ, int NB>
 __global__ void __launch_bounds__(256) bsr_mfma_ell_kernel(const BsrArgs p, long ntiles_n) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    typedef typename BsrMfmaElem<R, CPLX>::type E; // the vectors; the values as stored, widening at the load:
+    typedef typename BsrStored<typename BsrMfmaElem<RV, CPLX>::type, E>::type EV;
     typedef typename BsrMfma<R>::acc_t acc_t;
     static_assert(BI <= 16 && BD % 4 == 0 && NNZ % NB == 0, "block shape");
     constexpr int KS = BD / 4, NG = NNZ / NB;
-    const E *__restrict__ v = (const E *)p.v;
+    const EV *__restrict__ v = (const EV *)p.v;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const int lane = threadIdx.x & 63;
@@ -431,7 +443,7 @@ __global__ void __launch_bounds__(256) bsr_mfma_ell_kernel(const BsrArgs p, long
             const int k = g * NB + u;
             const bool ok = dj[k] >= 0;
             const long d0 = ok ? dj[k] : 0;
-            const E *vb = v + (jb + k) * (BI * BD);
+            const EV *vb = v + (jb + k) * (BI * BD);
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const int e = ks * 4 + kq;
@@ -477,7 +489,7 @@ __global__ void __launch_bounds__(256) bsr_mfma_ell_kernel(const BsrArgs p, long
     }
 }
 
-template <typename R, bool CPLX, int BI, int BD, int NNZ, int NB>
+template <typename RV, typename R, bool CPLX, int BI, int BD, int NNZ, int NB>
 void launch_bsr_mfma_ell(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
     const long ntn = (a.ncols + 15) / 16;
     const long waves = a.block_rows * ntn;
@@ -486,17 +498,17 @@ void launch_bsr_mfma_ell(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) 
     g_bsr_tune.last = 10;
     KernelTimer timer("bsr", s);
     if (yrow && xrow)
-        hipLaunchKernelGGL((bsr_mfma_ell_kernel<R, CPLX, BI, BD, true, true, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_ell_kernel<RV, R, CPLX, BI, BD, true, true, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else if (yrow && !xrow)
-        hipLaunchKernelGGL((bsr_mfma_ell_kernel<R, CPLX, BI, BD, true, false, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_ell_kernel<RV, R, CPLX, BI, BD, true, false, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else if (!yrow && xrow)
-        hipLaunchKernelGGL((bsr_mfma_ell_kernel<R, CPLX, BI, BD, false, true, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_ell_kernel<RV, R, CPLX, BI, BD, false, true, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else
-        hipLaunchKernelGGL((bsr_mfma_ell_kernel<R, CPLX, BI, BD, false, false, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_ell_kernel<RV, R, CPLX, BI, BD, false, false, NNZ, NB>), dim3(blocks), dim3(256), 0, s, a, ntn);
     SBX_HIP_CHECK(hipGetLastError());
 }
 
-template <typename R, bool CPLX, int BI, int BD>
+template <typename RV, typename R, bool CPLX, int BI, int BD>
 void launch_bsr_mfma_pf(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
     const long ntn = (a.ncols + 15) / 16;
     const long waves = a.block_rows * ntn;
@@ -505,13 +517,13 @@ void launch_bsr_mfma_pf(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
     g_bsr_tune.last = 11;
     KernelTimer timer("bsr", s);
     if (yrow && xrow)
-        hipLaunchKernelGGL((bsr_mfma_pf_kernel<R, CPLX, BI, BD, true, true>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_pf_kernel<RV, R, CPLX, BI, BD, true, true>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else if (yrow && !xrow)
-        hipLaunchKernelGGL((bsr_mfma_pf_kernel<R, CPLX, BI, BD, true, false>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_pf_kernel<RV, R, CPLX, BI, BD, true, false>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else if (!yrow && xrow)
-        hipLaunchKernelGGL((bsr_mfma_pf_kernel<R, CPLX, BI, BD, false, true>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_pf_kernel<RV, R, CPLX, BI, BD, false, true>), dim3(blocks), dim3(256), 0, s, a, ntn);
     else
-        hipLaunchKernelGGL((bsr_mfma_pf_kernel<R, CPLX, BI, BD, false, false>), dim3(blocks), dim3(256), 0, s, a, ntn);
+        hipLaunchKernelGGL((bsr_mfma_pf_kernel<RV, R, CPLX, BI, BD, false, false>), dim3(blocks), dim3(256), 0, s, a, ntn);
     SBX_HIP_CHECK(hipGetLastError());
 }
 
@@ -527,14 +539,26 @@ void launch_bsr_mfma_pf(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
 // lanes address either array (a buffer load takes one array per instruction) -- 2304 instead of
 // 4096 bytes per complex<float> slot at 12 rhs, 4608 instead of 6144 for complex<double>, so more
 // waves (and more bytes in flight) fit a CU's LDS
-template <typename R, bool CPLX, int BI, int BD, bool YROW, int NNZ, int PD, bool M3, int PK = 0>
+// Mixed products (RV narrower than R: float -> double, f16 -> float): the slot holds the value
+// block as it lies in memory, in the operator's type EV (a complex32 block is 576 bytes, a float16
+// one 288: less than one DMA instruction), and the x block in E; the fragment reads take EV from
+// LDS and widen it (exact) in registers.  The value part's bytes, instruction count and the offset
+// of the x part follow from sizeof(EV), the x part's from sizeof(E): unpacked, each part rounded up
+// to 1 KB (both parts are 16-byte multiples for every pair); packed, PK = the slot's bytes / 1024
+// rounded up, 1..5 by the pair and the column count (complex32 at 12 rhs: 576 + 1152 bytes, PK 2).
+// Mixed products take the 4-multiplication complex form.
+template <typename RV, typename R, bool CPLX, int BI, int BD, bool YROW, int NNZ, int PD, bool M3, int PK = 0>
 __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsigned v_bytes, unsigned x_bytes) {
-    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    typedef typename BsrMfmaElem<R, CPLX>::type E; // the vectors; the values as stored, widening at the load:
+    typedef typename BsrStored<typename BsrMfmaElem<RV, CPLX>::type, E>::type EV;
     typedef typename BsrMfma<R>::acc_t acc_t;
     static_assert(BI <= 16 && BD % 4 == 0, "block shape");
-    constexpr int KS = BD / 4, ES = (int)sizeof(E);
+    constexpr bool SAME = std::is_same<RV, R>::value;
+    static_assert(SAME || !M3, "mixed products: 4 multiplications");
+    constexpr int KS = BD / 4, ES = (int)sizeof(E), EVS = (int)sizeof(EV);
     constexpr int ABLK = BI * BD, XBLK = BD * 16;        // elements (x: up to 16 cols)
-    constexpr int NA = (ABLK * ES + 1023) / 1024, NX = (XBLK * ES + 1023) / 1024; // DMA instructions
+    static_assert((ABLK * EVS) % 16 == 0, "a value block is whole 16-byte pieces");
+    constexpr int NA = (ABLK * EVS + 1023) / 1024, NX = (XBLK * ES + 1023) / 1024; // DMA instructions
     constexpr int NI = PK > 0 ? PK : NA + NX;            // DMA instructions per block
     extern __shared__ __attribute__((aligned(16))) char smem[];
     E *__restrict__ y = (E *)p.y;
@@ -543,7 +567,9 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
     if (i >= p.block_rows) return;
     const int nc = (int)p.ncols, xblk = BD * nc;
     // bytes per ring slot (packed: values then x, 16-byte aligned)
-    const unsigned SLOT = PK > 0 ? (unsigned)(ABLK + xblk) * ES : (unsigned)(NA + NX) * 1024u;
+    const unsigned SLOT = PK == 0 ? (unsigned)(NA + NX) * 1024u
+                          : SAME  ? (unsigned)(ABLK + xblk) * ES
+                                  : (unsigned)(ABLK * EVS + xblk * ES);
     const long jb = i * NNZ;
     int dj[NNZ];
 #pragma unroll
@@ -551,13 +577,13 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
     // the row's NNZ value blocks (one contiguous run) as the buffer: 32-bit offsets at any size
     (void)v_bytes;
     const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)((const E *)p.v + jb * ABLK), (short)0, NNZ * ABLK * ES, 0x00020000);
+        (void *)((const EV *)p.v + jb * ABLK), (short)0, NNZ * ABLK * EVS, 0x00020000);
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)p.x, (short)0, (int)x_bytes, 0x00020000);
     const unsigned slot0 = lds_u32(smem) + (unsigned)w * (SLOT * (PD + 1));
     auto issue = [&](int k) {
         const unsigned base = slot0 + (unsigned)(k % (PD + 1)) * SLOT;
         if constexpr (PK > 0) {
-            const char *vrow = (const char *)((const E *)p.v + (jb + k) * ABLK);
+            const char *vrow = (const char *)((const EV *)p.v + (jb + k) * ABLK);
             // a skipped block (column -1) reads x's first block row (not used): always BD * nc
             // valid elements, where the block's own values may end before the slot's x part
             const char *xrow = (const char *)((const E *)p.x + (long)(dj[k] < 0 ? 0 : dj[k]) * nc);
@@ -565,9 +591,9 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
             for (int q = 0; q < PK; ++q) {
                 const unsigned g = (unsigned)(lane + 64 * q) * 16u;
                 if (g < SLOT) {
-                    const char *src = g < (unsigned)(ABLK * ES) ? vrow + g : xrow + (g - ABLK * ES);
+                    const char *src = g < (unsigned)(ABLK * EVS) ? vrow + g : xrow + (g - ABLK * EVS);
                     // nt on the instructions that carry values only (x rows are reused)
-                    if ((p.nt & 1) && (q + 1) * 1024 <= ABLK * ES)
+                    if ((p.nt & 1) && (q + 1) * 1024 <= ABLK * EVS)
                         asm volatile("s_mov_b32 m0, %1\n\t"
                                      "s_nop 0\n\t"
                                      "global_load_lds_dwordx4 %0, off nt"
@@ -584,11 +610,11 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
                 }
             }
         } else {
-            const unsigned av = (unsigned)(k * ABLK * ES), xv = (unsigned)((long)(dj[k] < 0 ? 0 : dj[k]) * nc) * ES;
+            const unsigned av = (unsigned)(k * ABLK * EVS), xv = (unsigned)((long)(dj[k] < 0 ? 0 : dj[k]) * nc) * ES;
 #pragma unroll
             for (int q = 0; q < NA; ++q) {
                 const unsigned g = (unsigned)(lane + 64 * q) * 16u;
-                dma16(rv, g < (unsigned)(ABLK * ES) ? av + g : 0x80000000u, base + (unsigned)q * 1024u, p.nt & 1);
+                dma16(rv, g < (unsigned)(ABLK * EVS) ? av + g : 0x80000000u, base + (unsigned)q * 1024u, p.nt & 1);
             }
 #pragma unroll
             for (int q = 0; q < NX; ++q) {
@@ -610,8 +636,8 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
         // block k landed: the NI instructions of each later block issued so far may stay in flight
         wait_vmcnt_n(NI * (NNZ - 1 - k < PD ? NNZ - 1 - k : PD));
         if (dj[k] < 0) continue;
-        const E *sa = (const E *)(smem + (slot0 - lds_u32(smem)) + (k % (PD + 1)) * SLOT);
-        const E *sx = sa + (PK > 0 ? ABLK : NA * 1024 / ES);
+        const EV *sa = (const EV *)(smem + (slot0 - lds_u32(smem)) + (k % (PD + 1)) * SLOT);
+        const E *sx = (const E *)(sa + (PK > 0 ? ABLK : NA * 1024 / EVS));
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int e = ks * 4 + kq;
@@ -693,17 +719,94 @@ bool launch_bsr_mfma_dma(const BsrArgs &a, bool yrow, hipStream_t s) {
     };
     if (packed && !m3) {
         constexpr int PKN = CPLX && ES == 16 ? 5 : 3;
-        if (yrow) go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, true, NNZ, PD, false, PKN>);
-        else go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, false, NNZ, PD, false, PKN>);
-    } else if (yrow && m3) go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, true, NNZ, PD, true>);
-    else if (yrow) go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, true, NNZ, PD, false>);
-    else if (m3) go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, false, NNZ, PD, true>);
-    else go(bsr_mfma_dma_kernel<R, CPLX, BI, BD, false, NNZ, PD, false>);
+        if (yrow) go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, true, NNZ, PD, false, PKN>);
+        else go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, false, NNZ, PD, false, PKN>);
+    } else if (yrow && m3) go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, true, NNZ, PD, true>);
+    else if (yrow) go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, true, NNZ, PD, false>);
+    else if (m3) go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, false, NNZ, PD, true>);
+    else go(bsr_mfma_dma_kernel<R, R, CPLX, BI, BD, false, NNZ, PD, false>);
     SBX_HIP_CHECK(hipGetLastError());
     return true;
 }
 
-template <typename R, bool CPLX, int BI, int BD>
+/// The same for a mixed product (values RV, vectors R).  Only with 16-byte aligned values and x (a
+/// DMA lane moves 16 bytes, and a float16 operator may start at any even address) and x blocks that
+/// are whole 16-byte pieces; false: not this shape.
+///  * form 7, unpacked slots: NA instructions of values (in RV) and NX of x (in R), each a whole
+///    64-lane pass of 16 bytes -- lanes past a part's bytes write zeros;
+///  * form 8, packed slots: values then x as one run of slot bytes, moved by PK = slot bytes / 1024
+///    (rounded up) instructions; the last one is masked to the slot.  PK follows from the pair and
+///    the column count (PKMIN..PKMAX: 1 and 16 columns).
+/// mixed12_pack 1 packs below 12 columns, where it was measured faster than unpacked slots by more
+/// than the spread (16^4 and 16^3 x 64, 1 and 4 columns: 2 % complex32, 8-10 % complex<float> values;
+/// at 12 and 16 columns a tie or up to 5 % slower, profiles/bsr_mixed12_measure.txt); 0 never, 2
+/// always.
+template <typename RV, typename R, bool CPLX, int BI, int BD, int NNZ, int PD>
+bool launch_bsr_mfma_dma_mixed(const BsrArgs &a, bool yrow, hipStream_t s) {
+    typedef typename BsrMfmaElem<RV, CPLX>::type EV;
+    typedef typename BsrMfmaElem<R, CPLX>::type E;
+    constexpr int ES = (int)sizeof(E), EVS = (int)sizeof(EV);
+    constexpr int NA = (BI * BD * EVS + 1023) / 1024, NX = (BD * 16 * ES + 1023) / 1024;
+    constexpr int PKMIN = (BI * BD * EVS + BD * ES + 1023) / 1024, PKMAX = (BI * BD * EVS + BD * 16 * ES + 1023) / 1024;
+    static_assert((BI * BD * EVS) % 16 == 0, "a value block is whole 16-byte pieces");
+    static_assert(PKMAX <= 5, "wait_vmcnt_n's counts");
+    const long v_bytes = a.block_rows * NNZ * (long)BI * BD * EVS, x_bytes = a.x_rows * a.ldx * (long)ES;
+    if (a.x_rows <= 0 || x_bytes >= (1L << 31)) return false;
+    const long blocks = (a.block_rows + 3) / 4;
+    if (blocks >= (1L << 31)) return false;
+    if (a.ncols < 1 || a.ncols > 16 || (BD * a.ncols * ES) % 16 != 0 || ((size_t)a.x & 15) != 0 ||
+        ((size_t)a.v & 15) != 0)
+        return false;
+    KernelTimer timer("bsr", s);
+    size_t lds = 0;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a, (unsigned)v_bytes, (unsigned)x_bytes);
+    };
+    if (g_bsr_tune.mixed12_pack >= 2 || (g_bsr_tune.mixed12_pack == 1 && a.ncols < 12)) {
+        // the kernel's issue loop: lane l of instruction q writes the 16 bytes at q * 1024 + 16 l of
+        // the slot when that offset is below the slot size (a 16-byte multiple): the pk instructions
+        // write exactly the slot, every one with a lane in range, in a ring of 4 waves x (PD + 1) slots
+        const long slot = (long)BI * BD * EVS + (long)BD * a.ncols * ES;
+        const int pk = (int)((slot + 1023) / 1024);
+        if (slot % 16 != 0 || pk < PKMIN || pk > PKMAX || (pk - 1) * 1024L >= slot)
+            throw Error("bsr: internal packed-slot sizing error in bsr_mfma_dma_kernel (mixed)");
+        lds = (size_t)4 * slot * (PD + 1);
+        check_dma_lds("bsr_mfma_dma_kernel (mixed, packed)", lds, 0, 0, 4L * (PD + 1) * std::min(pk * 1024L, slot));
+        g_bsr_tune.last = 8;
+        auto at = [&](auto pkc) {
+            constexpr int P = decltype(pkc)::value;
+            if constexpr (P >= PKMIN && P <= PKMAX) {
+                if (pk == P) {
+                    if (yrow) go(bsr_mfma_dma_kernel<RV, R, CPLX, BI, BD, true, NNZ, PD, false, P>);
+                    else go(bsr_mfma_dma_kernel<RV, R, CPLX, BI, BD, false, NNZ, PD, false, P>);
+                }
+            }
+        };
+        at(std::integral_constant<int, 1>{});
+        at(std::integral_constant<int, 2>{});
+        at(std::integral_constant<int, 3>{});
+        at(std::integral_constant<int, 4>{});
+        at(std::integral_constant<int, 5>{});
+    } else {
+        // 4 waves x (PD + 1) ring slots of NA + NX whole instructions
+        lds = (size_t)4 * (NA + NX) * 1024 * (PD + 1);
+        check_dma_lds("bsr_mfma_dma_kernel (mixed)", lds, 4L * (PD + 1) * (NA + NX), 64);
+        g_bsr_tune.last = 7;
+        if (yrow) go(bsr_mfma_dma_kernel<RV, R, CPLX, BI, BD, true, NNZ, PD, false>);
+        else go(bsr_mfma_dma_kernel<RV, R, CPLX, BI, BD, false, NNZ, PD, false>);
+    }
+    SBX_HIP_CHECK(hipGetLastError());
+    return true;
+}
+
+/// launch_bsr_mfma_dma for either kind of product
+template <typename RV, typename R, bool CPLX, int BI, int BD, int NNZ, int PD>
+bool launch_bsr_mfma_dma_any(const BsrArgs &a, bool yrow, hipStream_t s) {
+    if constexpr (std::is_same<RV, R>::value) return launch_bsr_mfma_dma<R, CPLX, BI, BD, NNZ, PD>(a, yrow, s);
+    else return launch_bsr_mfma_dma_mixed<RV, R, CPLX, BI, BD, NNZ, PD>(a, yrow, s);
+}
+
+template <typename RV, typename R, bool CPLX, int BI, int BD>
 void launch_bsr_mfma(const BsrArgs &a, int nnz, bool yrow, bool xrow, hipStream_t s) {
     // contiguous x blocks (row-major x, ldx == ncols <= 16), 9 blocks per row: the blocks staged
     // by LDS-DMA one ahead (16^4 complex<double> n = 12: 426 us for the round-1 fragment kernel,
@@ -714,15 +817,15 @@ void launch_bsr_mfma(const BsrArgs &a, int nnz, bool yrow, bool xrow, hipStream_
     // every W-th row through an 8-slot ring, 787-1221 against 695 us -- both removed again,
     // profiles/r06_bsr12_vreg_chain.txt, r06_bsr12_stream_chain.txt, commit ad3532b)
     if (g_bsr_tune.variant == 0 && nnz == 9 && xrow && a.ldx == a.ncols && a.ncols <= 16 &&
-        (g_bsr_tune.blk_pd == 2   ? launch_bsr_mfma_dma<R, CPLX, BI, BD, 9, 2>(a, yrow, s)
-         : g_bsr_tune.blk_pd == 3 ? launch_bsr_mfma_dma<R, CPLX, BI, BD, 9, 3>(a, yrow, s)
-                                  : launch_bsr_mfma_dma<R, CPLX, BI, BD, 9, 1>(a, yrow, s)))
+        (g_bsr_tune.blk_pd == 2   ? launch_bsr_mfma_dma_any<RV, R, CPLX, BI, BD, 9, 2>(a, yrow, s)
+         : g_bsr_tune.blk_pd == 3 ? launch_bsr_mfma_dma_any<RV, R, CPLX, BI, BD, 9, 3>(a, yrow, s)
+                                  : launch_bsr_mfma_dma_any<RV, R, CPLX, BI, BD, 9, 1>(a, yrow, s)))
         return;
     // the 9-point stencils otherwise: columns preloaded, fragments one block ahead (a 3- or
     // 9-block lookahead, the XCD-grouped row order and non-temporal value loads were all
     // measured slower, non-temporal stores of y no faster); any other pattern: generic rows
-    if (g_bsr_tune.variant != 1 && nnz == 9) return launch_bsr_mfma_ell<R, CPLX, BI, BD, 9, 1>(a, yrow, xrow, s);
-    launch_bsr_mfma_pf<R, CPLX, BI, BD>(a, yrow, xrow, s);
+    if (g_bsr_tune.variant != 1 && nnz == 9) return launch_bsr_mfma_ell<RV, R, CPLX, BI, BD, 9, 1>(a, yrow, xrow, s);
+    launch_bsr_mfma_pf<RV, R, CPLX, BI, BD>(a, yrow, xrow, s);
 }
 
 template <typename E, int BI, int BD, int G>
@@ -1766,11 +1869,25 @@ bool launch_blk(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s, const int
 /// the k-step of 16, the work of a 32x32 block); between the measured sizes by the block's
 /// elements, more than 256 and fewer than 1024 from 12 columns (float16 -> float: the same
 /// bound, carried over, not measured).
-/// blk_mfma 2: no column bound.  3x3 and 12x12 blocks and everything else run the generic mixed
-/// form.
+/// blk_mfma 2: no column bound.
+/// 12x12 blocks (the lattice's fine operator) from mixed12_min_cols rhs columns on take the
+/// choices of launch_bsr_mfma with the values read in EV: the LDS-DMA form (7, or 8 with packed
+/// slots, mixed12_pack; variant 0, 9 blocks per row, row-major x with ldx == ncols <= 16, blk_pd
+/// blocks ahead, values and x 16-byte aligned), the fragment gathers (10; 9 blocks per row) or the
+/// generic rows (11; variant 1, any pattern); gemm.m3 does not apply (always 4 multiplications).
+/// Measured against the generic mixed form (16^4 and 16^3 x 64 9-point operators, complex32 ->
+/// complex<float> and complex<float> -> complex<double>, profiles/bsr_mixed12_measure.txt): faster
+/// at every column count, 1.6-2.4x at 1 and 4 columns, 3.7-7.1x from 12, far beyond the spreads.
+/// The default bound of 4 columns is a condition (tests pin 12x12 at 3 columns on the generic
+/// form), not a crossover.  Against the same values widened on the same-type kernels the time
+/// does not follow the bytes: 0.89-1.23x (see the profile).
+/// 3x3 blocks and everything else run the generic mixed form.
 template <typename EV, typename EX>
-void launch_mixed(const BsrArgs &a, bool yrow, bool xrow, hipStream_t s) {
+void launch_mixed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipStream_t s) {
     constexpr bool HALF = std::is_same<EV, f16>::value || std::is_same<EV, f16x2>::value;
+    if (g_bsr_tune.mixed && a.bi == 12 && a.bd == 12 && a.ncols >= g_bsr_tune.mixed12_min_cols)
+        return launch_bsr_mfma<typename BsrMfmaScalar<EV>::real, typename BsrMfmaScalar<EX>::real,
+                               BsrMfmaScalar<EX>::cplx, 12, 12>(a, nnz_per_row, yrow, xrow, s);
     const long be = (long)a.bi * a.bd;
     const int min_cols = g_bsr_tune.blk_mfma >= 2 || be >= 32 * 32 ? 1 : HALF && be > 16 * 16 ? 12 : 4;
     if (g_bsr_tune.mixed && g_bsr_tune.blk_mfma && g_bsr_tune.variant != 1 && a.bi >= g_bsr_tune.blk_min &&
@@ -1799,7 +1916,8 @@ void launch_typed(const BsrArgs &a, int nnz_per_row, bool yrow, bool xrow, hipSt
     else if (a.bi == 12 && a.bd == 12)
         // one block row per wave: interleaving 2 or 4 rows per wave measured 6 % / 25 % slower
         // (more VGPRs, fewer waves to hide the HBM latency of the value stream)
-        launch_bsr_mfma<typename BsrMfmaScalar<E>::real, BsrMfmaScalar<E>::cplx, 12, 12>(a, nnz_per_row, yrow, xrow, s);
+        launch_bsr_mfma<typename BsrMfmaScalar<E>::real, typename BsrMfmaScalar<E>::real, BsrMfmaScalar<E>::cplx, 12, 12>(
+            a, nnz_per_row, yrow, xrow, s);
     // dense blocks from blk_min x blk_min on: bsr_blk_mfma_kernel where it was measured faster
     // than the generic kernel by more than the round-to-round spread (8^4 9-point operators,
     // complex<float> and complex<double>, profiles/bsr_blocks_measure.txt): 32x32 blocks and
@@ -1913,13 +2031,13 @@ void launch_bsr(const BsrDesc &d, int device) {
         // single-precision values with double-precision vectors, half-precision values with
         // single-precision vectors (bsr_krylov admits these four pairs)
         if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE)
-            return launch_mixed<float2, double2>(a, d.y_row_major, d.x_row_major, s);
+            return launch_mixed<float2, double2>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);
         if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE)
-            return launch_mixed<float, double>(a, d.y_row_major, d.x_row_major, s);
+            return launch_mixed<float, double>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);
         if (d.tv == SBX_CHALF && d.t == SBX_CFLOAT)
-            return launch_mixed<f16x2, float2>(a, d.y_row_major, d.x_row_major, s);
+            return launch_mixed<f16x2, float2>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);
         if (d.tv == SBX_HALF && d.t == SBX_FLOAT)
-            return launch_mixed<f16, float>(a, d.y_row_major, d.x_row_major, s);
+            return launch_mixed<f16, float>(a, d.num_nnz_per_row, d.y_row_major, d.x_row_major, s);
         throw Error("bsr: unsupported pair of value and vector types");
     }
     switch (d.t) {

@@ -349,7 +349,21 @@ struct BsrTune {
                    ///< admit go to bsr_blk_mfma_kernel's mixed form where it was measured faster (blocks of
                    ///< 1024 elements and more at any column count, smaller ones from 4 rhs columns;
                    ///< blk_mfma 2: at any column count), 0 = every mixed product on the generic
-                   ///< mixed kernel
+                   ///< mixed kernel.  Half-precision operators (float16 -> float, complex32 ->
+                   ///< complex<float>) go the same way.  12x12 blocks: see mixed12_min_cols
+    long mixed12_min_cols = 4; ///< mixed products of 12x12 blocks (all four pairs) from this many rhs columns on
+                               ///< run the 12x12 matrix-core kernels with the values read in their own type
+                               ///< (variant, blk_pd and the x layout choose among forms 7, 10 and 11 as for
+                               ///< same-type products), fewer columns the generic mixed kernel.  1 = at any
+                               ///< column count.  The default is a condition, not a measured crossover: a
+                               ///< 16-column MFMA tile holding at most 3 columns is under 19 % used
+                               ///< (measured, profiles/bsr_mixed12_measure.txt: the matrix-core kernels
+                               ///< beat the generic mixed kernel at every column count, 1.6-2.4x at 1 and
+                               ///< 4 columns, 3.7-7.1x from 12)
+    int mixed12_pack = 1; ///< ... the ring slots of their LDS-DMA form (row-major x, at most 16 columns):
+                          ///< packed (values then x in one run, last_kernel 8) or each part rounded up to
+                          ///< 1 KB (7).  1 = packed below 12 columns, where it was measured faster (2-10 %
+                          ///< at 1 and 4 columns; a tie or slower at 12 and 16), 0 = never, 2 = always
     int adj_inplace = 0; ///< A^H of operators made by create_bsr (x with the image labels), read at
                          ///< each product: 0 = through a conjugated, regrouped copy of the value
                          ///< blocks made at the first such product (a snapshot; A's own kernels
@@ -374,7 +388,8 @@ struct BsrTune {
     /// values and double-precision vectors on MFMA (bsr_blk_mfma_kernel, values narrower),
     /// 17 the in-place adjoint of dense blocks on MFMA (bsr_blk_mfma_kernel, ADJ), 18 the in-place
     /// adjoint, a thread per output element (bsr_kernel, ADJ),
-    /// 0 another kernel
+    /// 0 another kernel.  7, 8, 10 and 11 with last_mixed 1: the same 12x12 kernels reading values of
+    /// the narrower type (mixed12_min_cols, mixed12_pack)
     std::atomic<int> last{0};
     /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type
     /// than its vectors, else 0
