@@ -632,13 +632,17 @@ void contraction(T alpha, const PartitionItem<Nd0> *p0, const Coor<Nd0> &from0,
 /// the same handle.  Every value is converted to double exactly where it is read -- in place, in
 /// the caller's array, no converted copy is kept -- and products, sums, alpha, beta and y are
 /// double: the result is the product of the up-converted operator with x.  Every other pair of
-/// types, and any type difference on an operator of create_kron_bsr, throws as before.
+/// types, and any type difference on an operator of create_kron_bsr, throws as before -- unless
+/// sbx_tune_set("bsr.kron_mixed", 1) (default 0, read at each bsr_krylov call): then an operator
+/// of create_kron_bsr<Nd, Ni, float> or <Nd, Ni, std::complex<float>> (colour values and spin
+/// matrices both in that type) is contracted with T the double counterpart in the same way, A x
+/// and A^H x, both arrays read in place and widened where they are read.
 /// The same one step down: an operator of create_bsr<Nd, Ni, float16> or
 /// <Nd, Ni, complex_float16> (IEEE binary16 values, above) is contracted by bsr_krylov with T =
 /// float / std::complex<float>; the values are widened to float exactly where they are read, and
 /// products, sums, alpha, beta and y are float.  binary16 holds magnitudes up to 65504 (smallest
 /// subnormal 2^-24): scale the operator into range and pass the scale in alpha.  Half operators
-/// with double vectors and create_kron_bsr with half values throw.
+/// with double vectors and create_kron_bsr with half values throw (whatever bsr.kron_mixed).
 ///
 /// The image side (x with the image labels, y = alpha A^H x) of a create_bsr operator: by default
 /// the first such product makes a conjugated, regrouped copy of the value blocks that all later

@@ -144,12 +144,19 @@ int sbx_timings_report(char *buf, int len);
    same bits as the kernels on the copy; the dense blocks "bsr.blk_mfma" admits on bsr_blk_mfma_kernel's adjoint form,
    everything else, the mixed pairs and 3x3 / 12x12 operators included, on bsr_kernel's; Kronecker
    operators ignore it, they are in place already),
+   "bsr.kron_mixed" (operators of sbx_create_kron_bsr in float / complex<float>, values and spin matrices,
+   applied to double / complex<double> vectors; read at each sbx_bsr_krylov call: 0, the default, refused --
+   any type difference on a Kronecker operator fails; 1 admitted, A x and A^H x, both arrays read in place and
+   widened at the load, products and sums in double; half-precision Kronecker values stay refused at creation
+   and the spin-first kernels of "bsr.kron_spin" are not taken),
    "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
    last BSR launch, sbx_internal.h BsrTune::last; 14 = bsr_blk_mfma_kernel; 16 with "bsr.last_mixed" 1 =
    its mixed form, 0 with it = the generic kernel bsr_kernel's mixed form, 7 / 8 / 10 / 11 with it = the 12x12
-   matrix-core kernels reading the narrower values; 17 = bsr_blk_mfma_kernel's and 18 =
+   matrix-core kernels reading the narrower values, 5 / 6 / 15 with it = the Kronecker kernels reading
+   single-precision values under "bsr.kron_mixed", 19 = the generic Kronecker adjoint kernel doing so (16 without
+   "bsr.last_mixed"); 17 = bsr_blk_mfma_kernel's and 18 =
    bsr_kernel's adjoint form, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
    by the value copies of transposed operators, process-wide: it grows when a copy is made and shrinks when
    its operator is destroyed; it cannot be set), "bsr.last_mixed" (1 when the last BSR

@@ -755,7 +755,9 @@ def bsr_krylov(alpha, bsr: BSR, oim: str, odm: str, px, ox: str, fromx, sizex, d
     The type is that of vx / vy.  Mixed precision (an extension): an operator of create_bsr in
     float32 / complex64 may be applied to float64 / complex128 vx and vy; its values are read in
     place, widened exactly where they are loaded, and the product is computed and written in
-    double (no converted copy is kept).  Any other difference of types raises."""
+    double (no converted copy is kept).  An operator of create_kron_bsr in float32 / complex64
+    (values and spin matrices) is admitted in the same way, A x and A^H x, under
+    tune_set("bsr.kron_mixed", 1) only (default 0).  Any other difference of types raises."""
     nx, ny = len(ox), len(oy)
     nc = len(vx)
     t = _dtype_of(list(vx) + list(vy))

@@ -804,14 +804,16 @@ void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const s
         if ((op.blocki[i] > 1 && op.blocki[i] != op.dimi[i]) ||
             (op.kroni[i] > 1 && op.kroni[i] != op.dimi[i]))
             throw Error("Still not supported partially blocking a dimension");
-    // x and y have the operator's type, or -- an extension, not for Kronecker operators -- a
-    // single-precision operator is applied to vectors of its double counterpart, or a
-    // half-precision one to vectors of its single counterpart: the values are read in place and
+    // x and y have the operator's type, or -- an extension -- a single-precision operator is
+    // applied to vectors of its double counterpart (a Kronecker operator under bsr.kron_mixed 1
+    // only, read here: its colour blocks and spin matrices), or a half-precision one (never a
+    // Kronecker operator) to vectors of its single counterpart: the values are read in place and
     // widened at the load, everything else (temporaries, halo exchange, copies) is in x's type
-    const bool mixed = !op.is_kron && ((op.dtype == SBX_FLOAT && x.dtype == SBX_DOUBLE) ||
-                                       (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE) ||
-                                       (op.dtype == SBX_HALF && x.dtype == SBX_FLOAT) ||
-                                       (op.dtype == SBX_CHALF && x.dtype == SBX_CFLOAT));
+    const bool to_double = (op.dtype == SBX_FLOAT && x.dtype == SBX_DOUBLE) ||
+                           (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE);
+    const bool mixed = op.is_kron ? to_double && g_bsr_tune.kron_mixed != 0
+                                  : to_double || (op.dtype == SBX_HALF && x.dtype == SBX_FLOAT) ||
+                                        (op.dtype == SBX_CHALF && x.dtype == SBX_CFLOAT);
     if (x.dtype != y.dtype || (x.dtype != op.dtype && !mixed))
         throw Error("bsr_krylov: type mismatch");
     const int dtype = x.dtype;
@@ -1024,7 +1026,9 @@ void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const s
                     d.kd = (int)volume(op.krond);
                     d.kron = bc.kron;
                     d.kron_perm = bc.kron_perm;
-                    if (bc.kron_terms_due && g_bsr_tune.kron_spin > 0) {
+                    // (the spin-first tables read the spin matrices as doubles: same-type
+                    // complex<double> products only, a mixed launch passes none)
+                    if (bc.kron_terms_due && g_bsr_tune.kron_spin > 0 && d.tv == d.t) {
                         // (first spin-first launch: the tables; one host thread at a time)
                         static std::mutex mu;
                         std::lock_guard<std::mutex> lock(mu);
@@ -1035,8 +1039,8 @@ void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const s
                             mc.kron_terms_due = false;
                         }
                     }
-                    d.kron_terms = bc.kron_terms;
-                    d.kron_xor = bc.kron_xor;
+                    d.kron_terms = d.tv == d.t ? bc.kron_terms : nullptr;
+                    d.kron_xor = d.tv == d.t ? bc.kron_xor : nullptr;
                     d.adj_ptr = bc.adj_ptr;
                     d.adj_ent = bc.adj_ent;
                     launch_bsr_kron(d, bc.dev);

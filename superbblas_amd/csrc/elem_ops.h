@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace sbx {
 namespace {
 
@@ -73,6 +75,29 @@ template <> struct Ops<f16x2> {
         return a;
     }
 };
+
+// A value of the operator's type EV as the vectors' type EX: itself, or an operator kept in
+// single precision (float, float2) widened to the double counterpart, or one kept in half
+// precision (f16, f16x2) widened to the single counterpart (both exact)
+__device__ __forceinline__ double widen(float a) { return (double)a; }
+__device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
+__device__ __forceinline__ float widen(f16 a) { return (float)a; }
+__device__ __forceinline__ float2 widen(f16x2 a) { return float2{(float)a.x, (float)a.y}; }
+template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
+    if constexpr (std::is_same<EX, EV>::value) return a;
+    else return widen(a);
+}
+
+/// An element of a narrower operator as it lies in memory (EV), read as the vectors' type EX: the
+/// load widens.  A same-type kernel's stored type is EX itself, so its loads are the plain ones
+/// (the 12x12 and the Kronecker matrix-core same-type kernels compile as before,
+/// profiles/bsr_mixed12_isa.txt, profiles/kron_mixed_isa.txt).
+template <typename EV, typename EX> struct BsrNarrow {
+    EV val;
+    __device__ __forceinline__ operator EX() const { return widen(val); }
+};
+template <typename EV, typename EX> struct BsrStored { typedef BsrNarrow<EV, EX> type; };
+template <typename EX> struct BsrStored<EX, EX> { typedef EX type; };
 
 /// Non-temporal (streaming) store of one element: the line is written through without being
 /// kept in the caches (outputs written once and not re-read by the same kernel)

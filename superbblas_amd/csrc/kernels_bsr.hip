@@ -46,17 +46,7 @@ struct BsrArgs {
     TileSched tiles[2];
 };
 
-// A value of the operator's type EV as the vectors' type EX: itself, or an operator kept in
-// single precision (float, float2) widened to the double counterpart, or one kept in half
-// precision (f16, f16x2) widened to the single counterpart (both exact)
-__device__ __forceinline__ double widen(float a) { return (double)a; }
-__device__ __forceinline__ double2 widen(float2 a) { return double2{(double)a.x, (double)a.y}; }
-__device__ __forceinline__ float widen(f16 a) { return (float)a; }
-__device__ __forceinline__ float2 widen(f16x2 a) { return float2{(float)a.x, (float)a.y}; }
-template <typename EX, typename EV> __device__ __forceinline__ EX to_vec(EV a) {
-    if constexpr (std::is_same<EX, EV>::value) return a;
-    else return widen(a);
-}
+// (widen / to_vec, a value of the operator's type as the vectors' type: elem_ops.h)
 
 // The generic form, any block size, pattern and layout: one thread per output element, for
 //  * same-type products (EV == EX; BI_, BD_ > 0: a compile-time block shape);
@@ -291,15 +281,7 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned off, u
                      : "memory", "m0");
 }
 
-/// An element of a narrower operator as it lies in memory (EV), read as the vectors' type EX: the
-/// load widens.  A same-type kernel's stored type is EX itself, so its loads are the plain ones
-/// (the 12x12 same-type kernels compile as before, profiles/bsr_mixed12_isa.txt).
-template <typename EV, typename EX> struct BsrNarrow {
-    EV val;
-    __device__ __forceinline__ operator EX() const { return widen(val); }
-};
-template <typename EV, typename EX> struct BsrStored { typedef BsrNarrow<EV, EX> type; };
-template <typename EX> struct BsrStored<EX, EX> { typedef EX type; };
+// (BsrNarrow / BsrStored, an element of a narrower operator as it lies in memory: elem_ops.h)
 
 template <typename R, bool CPLX> struct BsrMfmaElem;
 template <> struct BsrMfmaElem<double, true> { typedef double2 type; };

@@ -40,10 +40,14 @@ struct KronArgs {
     const void *xtab; ///< ... as diagonal + XOR partner (nullptr: not of that form)
 };
 
-template <typename E, int BI, int BD, int KI, int KD>
+// Mixed precision (bsr.kron_mixed): every kernel of this file but the spin-first ones has a value
+// type EV beside the vector type E -- EV = E, or float / float2 under double / double2.  The
+// colour blocks v and the spin matrices kron are read in place as EV and widened (to_vec, exact)
+// where they are read; x, y, products, sums and alpha are E.  No converted copy exists.
+template <typename EV, typename E, int BI, int BD, int KI, int KD>
 __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ kron = (const E *)p.kron;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EV *__restrict__ kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const long total = p.block_rows * p.ncols;
@@ -64,7 +68,7 @@ __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
 #pragma unroll
                 for (int b = 0; b < KD; ++b) xv[d][b] = xs[d * xrow + b];
             // spin first: xk(d, a) = sum_b K_mu(a, b) x(d, b)
-            const E *K = kron + (long)mu * KI * KD;
+            const EV *K = kron + (long)mu * KI * KD;
             E xk[BD][KI];
 #pragma unroll
             for (int d = 0; d < BD; ++d)
@@ -74,18 +78,18 @@ __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
             for (int a = 0; a < KI; ++a)
 #pragma unroll
                 for (int b = 0; b < KD; ++b) {
-                    const E k = p.block_im_fast ? K[a + b * KI] : K[a * KD + b];
+                    const E k = to_vec<E>(p.block_im_fast ? K[a + b * KI] : K[a * KD + b]);
                     if (!Ops<E>::nonzero(k)) continue;
 #pragma unroll
                     for (int d = 0; d < BD; ++d) xk[d][a] = Ops<E>::fma(k, xv[d][b], xk[d][a]);
                 }
             // color: acc(i, a) += sum_d U(i, d) xk(d, a)
-            const E *U = v + j * BI * BD;
+            const EV *U = v + j * BI * BD;
 #pragma unroll
             for (int i = 0; i < BI; ++i)
 #pragma unroll
                 for (int d = 0; d < BD; ++d) {
-                    const E u = p.block_im_fast ? U[i + d * BI] : U[i * BD + d];
+                    const E u = to_vec<E>(p.block_im_fast ? U[i + d * BI] : U[i * BD + d]);
 #pragma unroll
                     for (int a = 0; a < KI; ++a) acc[i][a] = Ops<E>::fma(u, xk[d][a], acc[i][a]);
                 }
@@ -145,14 +149,16 @@ template <> struct Uniform<float2> {
 /// through L1), the spin matrices are read through the constant address space so that they live
 /// in SGPRs (wave-uniform operands of the FMAs), and the x values of the next nonzero are loaded
 /// while the current one is being applied (the loop over the NNZ nonzeros is unrolled).
-template <typename E, int BI, int BD, int KI, int KD, int NNZ>
+/// Mixed: the LDS image Us holds the values as stored (EV: half the LDS), widened at the LDS read;
+/// the spin matrices are scalar loads of EV, widened on the scalar side's way into the FMAs.
+template <typename EV, typename E, int BI, int BD, int KI, int KD, int NNZ>
 __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int S, int cpg) {
     extern __shared__ char smem[];
     constexpr int BLK = BI * BD * NNZ;
-    E *Us = (E *)smem;
+    EV *Us = (EV *)smem;
     int *Js = (int *)(Us + (long)S * BLK);
-    const E *__restrict__ v = (const E *)p.v;
-    const E *kron = (const E *)p.kron;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EV *kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     // consecutive chunks of block rows on one XCD: neighbouring sites share x lines in its L2
@@ -163,7 +169,7 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
     const long r0 = (long)gx * S;
     const int nrows = (int)std::min<long>(S, p.block_rows - r0);
     {
-        const E *src = v + r0 * BLK;
+        const EV *src = v + r0 * BLK;
         for (int e = threadIdx.x; e < nrows * BLK; e += 256) Us[e] = src[e];
         const int *jsrc = p.jj + r0 * NNZ;
         for (int e = threadIdx.x; e < nrows * NNZ; e += 256) Js[e] = jsrc[e];
@@ -180,7 +186,7 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
     for (int i = 0; i < BI; ++i)
 #pragma unroll
         for (int a = 0; a < KI; ++a) acc[i][a] = Ops<E>::zero();
-    const E *Ur = Us + sl * BLK;
+    const EV *Ur = Us + sl * BLK;
     const int *Jr = Js + sl * NNZ;
     E xa[BD][KD];
     {
@@ -200,8 +206,8 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
 #pragma unroll
                 for (int b = 0; b < KD; ++b) xb[d][b] = xs[d * xrow + b];
         }
-        const E *K = kron + mu * KI * KD;
-        const E *U = Ur + mu * BI * BD;
+        const EV *K = kron + mu * KI * KD;
+        const EV *U = Ur + mu * BI * BD;
 #pragma unroll
         for (int d = 0; d < BD; ++d) {
             // spin: xk(a) = sum_b K_mu(a, b) x(d, b)
@@ -212,13 +218,13 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
 #pragma unroll
                 for (int b = 0; b < KD; ++b)
                     xk[a] = Ops<E>::fma(
-                        Uniform<E>::load(K, p.block_im_fast ? a + b * KI : a * KD + b), xa[d][b],
-                        xk[a]);
+                        to_vec<E>(Uniform<EV>::load(K, p.block_im_fast ? a + b * KI : a * KD + b)),
+                        xa[d][b], xk[a]);
             }
             // color: acc(i, a) += U(i, d) xk(a)
 #pragma unroll
             for (int i = 0; i < BI; ++i) {
-                const E u = p.block_im_fast ? U[i + d * BI] : U[i * BD + d];
+                const E u = to_vec<E>(p.block_im_fast ? U[i + d * BI] : U[i * BD + d]);
 #pragma unroll
                 for (int a = 0; a < KI; ++a) acc[i][a] = Ops<E>::fma(u, xk[a], acc[i][a]);
             }
@@ -242,10 +248,10 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
 }
 
 /// Any block / Kronecker sizes: one thread per output element (block row, i, column, a)
-template <typename E>
+template <typename EV, typename E>
 __global__ void __launch_bounds__(256) bsr_kron_generic_kernel(const KronArgs p) {
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ kron = (const E *)p.kron;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EV *__restrict__ kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const long total = p.block_rows * p.bi * p.ncols * p.ki;
@@ -260,14 +266,14 @@ __global__ void __launch_bounds__(256) bsr_kron_generic_kernel(const KronArgs p)
         for (int mu = 0; mu < p.nnz; ++mu) {
             const long j = r * p.nnz + mu;
             const E *xs = x + (long)p.jj[j] * p.bd * p.ncols * p.kd + c * p.kd;
-            const E *K = kron + (long)mu * p.ki * p.kd;
-            const E *U = v + j * p.bi * p.bd;
+            const EV *K = kron + (long)mu * p.ki * p.kd;
+            const EV *U = v + j * p.bi * p.bd;
             for (int b = 0; b < p.kd; ++b) {
-                const E k = p.block_im_fast ? K[a + b * p.ki] : K[a * p.kd + b];
+                const E k = to_vec<E>(p.block_im_fast ? K[a + b * p.ki] : K[a * p.kd + b]);
                 if (!Ops<E>::nonzero(k)) continue;
                 E s = Ops<E>::zero();
                 for (int d = 0; d < p.bd; ++d) {
-                    const E u = p.block_im_fast ? U[i + d * p.bi] : U[i * p.bd + d];
+                    const E u = to_vec<E>(p.block_im_fast ? U[i + d * p.bi] : U[i * p.bd + d]);
                     s = Ops<E>::fma(u, xs[d * p.ncols * p.kd + b], s);
                 }
                 acc = Ops<E>::fma(k, s, acc);
@@ -294,9 +300,20 @@ __global__ void __launch_bounds__(256) bsr_kron_generic_kernel(const KronArgs p)
 // 2 waves per SIMD.
 // XL > 0: x staged by LDS-DMA in whole 64-B spin pieces, XL neighbours ahead (see
 // bsr_kron_mfma_packed_kernel)
-template <int NNZ, bool kpf = false, int XL = 0>
+// EV = float2 (complex<float> values under complex<double> vectors, bsr.kron_mixed): only the
+// colour run and the spin operand's source change.  The run sits in LDS as stored (8-byte values,
+// half the LDS) and is widened at the LDS read; it is staged by plain 8-byte loads and LDS
+// writes, not by LDS-DMA: the DMA moves 16-byte pieces, and a run of 8-byte values starts at
+// rlo * 81 * 8 bytes of a tensor that is itself only 8-byte aligned -- no multiple of 16 for an odd
+// rlo (40 columns: ngroups 3, rlo = floor(4 wgi / 3)) or an odd base.  The loads are bounded by
+// the run (e < nu), so nothing past the value array is read, whatever its alignment or length;
+// at most two loads a lane, once per workgroup, before the x ring starts.  The spin matrices are
+// widened where the ks image is filled (XL) or where they are loaded.
+template <int NNZ, bool kpf = false, int XL = 0, typename EV = double2>
 __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, int ngroups) {
     typedef double2 E;
+    constexpr bool same = std::is_same<EV, E>::value;
+    typedef typename BsrStored<EV, E>::type SV; // a value as stored: reading it as E widens
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const int lane = threadIdx.x & 63;
@@ -314,39 +331,44 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
     // the color blocks of the workgroup's rows (rows of a task group are consecutive: one
     // contiguous run) into LDS by one DMA pass, read back as broadcasts
     // (rounded up to whole DMA passes of 256 lanes: the lanes past the run write zeros)
-    __shared__ __attribute__((aligned(16))) E us[(4 * NNZ * 9 + 255) / 256 * 256];
+    __shared__ __attribute__((aligned(16))) EV us[(4 * NNZ * 9 + 255) / 256 * 256];
     // a workgroup's 4 tasks span at most 4 rows: nu <= 4 * NNZ * 9, every pass of 256 lanes fits
-    static_assert(sizeof(us) / sizeof(E) >= (4 * NNZ * 9 + 255) / 256 * 256, "LDS sizing");
+    static_assert(sizeof(us) / sizeof(EV) >= (4 * NNZ * 9 + 255) / 256 * 256, "LDS sizing");
     // XL: the spin matrices in LDS -- no vector-memory load in the main loop, where the
     // compiler's own vmcnt waits (blind to the DMAs) would drain the x ring
     __shared__ __attribute__((aligned(16))) E ks[XL ? NNZ * 16 : 1];
     if constexpr (XL > 0)
-        for (int e = (int)threadIdx.x; e < NNZ * 16; e += 256) ks[e] = ((const E *)p.kron)[e];
+        for (int e = (int)threadIdx.x; e < NNZ * 16; e += 256) ks[e] = ((const SV *)p.kron)[e];
     {
         const long rlo = (wgi * 4) / ngroups, rhi = min((wgi * 4 + 3) / ngroups, p.block_rows - 1);
-        const int nu = (int)(rhi - rlo + 1) * NNZ * 9;
-        // (launcher: the value array is below 2 GiB)
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
-        const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)us +
-                              (unsigned)w * 1024u;
-        for (int u = 0; u * 256 < nu; ++u) {
-            const int e = u * 256 + (int)threadIdx.x;
-            const unsigned off = e < nu ? (unsigned)(rlo * NNZ * 9 + e) * 16u : 0x80000000u;
-            asm volatile("s_mov_b32 m0, %1\n\t"
-                         "s_nop 0\n\t"
-                         "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                         :
-                         : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)(u * 256) * 16u)),
-                           "s"(rs)
-                         : "memory", "m0");
+        const int nu = (int)(rhi - rlo + 1) * NNZ * 9; // <= 4 * NNZ * 9 <= the elements of us
+        if constexpr (!same) {
+            const EV *__restrict__ src = (const EV *)p.v + rlo * NNZ * 9;
+            for (int e = (int)threadIdx.x; e < nu; e += 256) us[e] = src[e];
+        } else {
+            // (launcher: the value array is below 2 GiB)
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
+            const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)us +
+                                  (unsigned)w * 1024u;
+            for (int u = 0; u * 256 < nu; ++u) {
+                const int e = u * 256 + (int)threadIdx.x;
+                const unsigned off = e < nu ? (unsigned)(rlo * NNZ * 9 + e) * 16u : 0x80000000u;
+                asm volatile("s_mov_b32 m0, %1\n\t"
+                             "s_nop 0\n\t"
+                             "buffer_load_dwordx4 %0, %2, 0 offen lds"
+                             :
+                             : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)(u * 256) * 16u)),
+                               "s"(rs)
+                             : "memory", "m0");
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         (void)nchunk;
     }
     if (r >= p.block_rows) return;
-    const E *urow_s = us + (r - (wgi * 4) / ngroups) * NNZ * 9;
+    const SV *urow_s = (const SV *)us + (r - (wgi * 4) / ngroups) * NNZ * 9;
     const int b = lane >> 4, q = lane & 15;
     const long n = p.ncols;
     const long col = (long)cg * 16 + q;
@@ -354,7 +376,7 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
     const long colc = ok ? col : n - 1;
     // spin matrices as the A operand: lane 16 k + 4 g + a holds K_mu(a, k)
     const int ka = lane & 3, kk = lane >> 4;
-    const E *kron = (const E *)p.kron;
+    const SV *kron = (const SV *)p.kron;
     const int kidx = p.block_im_fast ? ka + kk * 4 : ka * 4 + kk;
     // block columns and color blocks of the row: wave-uniform
     const ConstPtr<int> jrow = (ConstPtr<int>)(p.jj + r * NNZ);
@@ -398,7 +420,7 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
     // the spin matrix of neighbour mu + 1 is loaded with its x rows; the compiler barrier keeps
     // the unrolled loop from hoisting all 9 spin-matrix loads to the top (36 more VGPRs: fewer
     // waves per SIMD)
-    E Kc = XL > 0 ? E{} : kron[kidx];
+    E Kc = XL > 0 ? E{} : E(kron[kidx]);
 #pragma unroll
     for (int mu = 0; mu < NNZ; ++mu) {
         if constexpr (kpf) asm volatile("" ::: "memory");
@@ -416,7 +438,7 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
             load_x(jrow[mu + 1], xb);
             if constexpr (kpf) Kn = kron[(mu + 1) * 16 + kidx];
         }
-        const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : kron[mu * 16 + kidx];
+        const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : E(kron[mu * 16 + kidx]);
         Kc = Kn;
         // color: T(i) = sum_d U(i, d) x(d)
         E t[3];
@@ -487,10 +509,16 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
 // the wave's ring (XL neighbours ahead, 3 KB per neighbour: deeper prefetch costs LDS, not
 // VGPRs), and the B lanes read them back with the spins rotated (position 4 q + (b + q / 2 +
 // q / 8) mod 4: the 16-B granules of any 8 or 16 lanes reading together fall on distinct banks).
-template <int NNZ, bool kpf = false, int XL = 0>
+// EV = float2 (bsr.kron_mixed): as in bsr_kron_mfma_kernel -- the colour run in LDS as stored,
+// staged by plain 8-byte loads bounded by the run and LDS writes (rw is even here, so the run's
+// start is a multiple of 16 from the base, but the base itself is only 8-byte aligned), widened
+// at the LDS read; the ks image widened where it is filled.
+template <int NNZ, bool kpf = false, int XL = 0, typename EV = double2>
 __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArgs p, int rw, int xring) {
     constexpr int NS = XL + 1;
     typedef double2 E;
+    constexpr bool same = std::is_same<EV, E>::value;
+    typedef typename BsrStored<EV, E>::type SV; // a value as stored: reading it as E widens
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const int lane = threadIdx.x & 63;
@@ -512,8 +540,12 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
     // the color blocks of the workgroup's rows (one contiguous run) into LDS by one DMA pass
     // (dynamic LDS: rw rows of NNZ 3x3 blocks)
     extern __shared__ __attribute__((aligned(16))) char smem_k[];
-    E *us = (E *)smem_k;
-    {
+    EV *us = (EV *)smem_k;
+    if constexpr (!same) {
+        const int nu = nrows * NNZ * 9; // <= rw * NNZ * 9: the launcher's LDS for the run
+        const EV *__restrict__ src = (const EV *)p.v + r0 * NNZ * 9;
+        for (int e = (int)threadIdx.x; e < nu; e += (int)blockDim.x) us[e] = src[e];
+    } else {
         const int nu = nrows * NNZ * 9;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
@@ -537,7 +569,7 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
 #pragma unroll
     for (int mu = 0; mu < NNZ; ++mu) jrow[mu] = p.jj[r * NNZ + mu];
     const int ka = lane & 3, kk = lane >> 4;
-    const E *kron = (const E *)p.kron;
+    const SV *kron = (const SV *)p.kron;
     const int kidx = p.block_im_fast ? ka + kk * 4 : ka * 4 + kk;
     const long xsite = 3 * n * 4;
     auto load_x = [&](int J, E *xv) {
@@ -594,12 +626,12 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    const E *urow_s = us + rlc * NNZ * 9;
+    const SV *urow_s = (const SV *)us + rlc * NNZ * 9;
     double accR[3] = {0, 0, 0}, accI[3] = {0, 0, 0};
     // the spin matrix of neighbour mu + 1 is loaded with its x rows; the compiler barrier keeps
     // the unrolled loop from hoisting all 9 spin-matrix loads to the top (36 more VGPRs: fewer
     // waves per SIMD)
-    E Kc = XL > 0 ? E{} : kron[kidx];
+    E Kc = XL > 0 ? E{} : E(kron[kidx]);
 #pragma unroll
     for (int mu = 0; mu < NNZ; ++mu) {
         if constexpr (kpf) asm volatile("" ::: "memory");
@@ -617,7 +649,7 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
             load_x(jrow[mu + 1], xb);
             if constexpr (kpf) Kn = kron[(mu + 1) * 16 + kidx];
         }
-        const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : kron[mu * 16 + kidx];
+        const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : E(kron[mu * 16 + kidx]);
         Kc = Kn;
         E t[3];
 #pragma unroll
@@ -1047,15 +1079,18 @@ constexpr int KRON_ADJ_CHUNK = 160, KRON_ADJ_SITES = 16, KRON_ADJ_STAGE_COLS = 3
 /// lanes consecutive columns, contiguous KI-element pieces -- one entry ahead, does the color
 /// product t(d, a) = sum_i conj(U(i, d)) x(i, a), then the spin product
 /// acc(d, b) += sum_a conj(K(a, b)) t(d, a), skipping the zeros of K.
-template <typename E, int BI, int BD, int KI, int KD, bool STAGE>
+/// Mixed (EV narrower than E, bsr.kron_mixed): the conj-transposed images Us and Ks are widened
+/// where they are staged, so the LDS layout and size are those of the same-type kernel of E and
+/// the main loop is unchanged; a lane reading its blocks itself widens at the load.
+template <typename EV, typename E, int BI, int BD, int KI, int KD, bool STAGE>
 __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, int S, int cpg) {
     extern __shared__ __attribute__((aligned(16))) char smem_a[];
     constexpr int BLK = BI * BD, KK = KI * KD, CH = STAGE ? KRON_ADJ_CHUNK : 0;
     E *Us = (E *)smem_a; // [CH][BD][BI] conj(U(i, d))
     E *Ks = Us + CH * BLK; // [nnz][KD][KI] conj(K(a, b))
     const int nth = (int)blockDim.x;
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ kron = (const E *)p.kron;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EV *__restrict__ kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const int tid = (int)threadIdx.x;
@@ -1063,7 +1098,7 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, 
     const int nrows = (int)std::min<long>(S, p.sites - r0);
     for (int e = tid; e < p.nnz * KK; e += nth) {
         const int mu = e / KK, w = e - mu * KK, b = w / KI, a = w - b * KI;
-        Ks[e] = Ops<E>::conj(kron[(long)mu * KK + (p.block_im_fast ? a + b * KI : a * KD + b)]);
+        Ks[e] = Ops<E>::conj(to_vec<E>(kron[(long)mu * KK + (p.block_im_fast ? a + b * KI : a * KD + b)]));
     }
     const int sl = tid / cpg;
     const long c = (long)blockIdx.y * cpg + tid % cpg;
@@ -1094,7 +1129,7 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, 
             for (int t = tid; t < n * BLK; t += nth) {
                 const int q = t / BLK, w = t - q * BLK, d = w / BI, i = w - d * BI;
                 const long k = p.ent[base + q];
-                Us[t] = Ops<E>::conj(v[k * BLK + (p.block_im_fast ? i + d * BI : i * BD + d)]);
+                Us[t] = Ops<E>::conj(to_vec<E>(v[k * BLK + (p.block_im_fast ? i + d * BI : i * BD + d)]));
             }
             __syncthreads();
         }
@@ -1108,12 +1143,12 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, 
             const int mu = k % p.nnz;
             E ug[BD][BI]; // not staged: the lane's own copy of the block
             if constexpr (!STAGE) {
-                const E *ub = v + (long)k * BLK;
+                const EV *ub = v + (long)k * BLK;
 #pragma unroll
                 for (int d = 0; d < BD; ++d)
 #pragma unroll
                     for (int i = 0; i < BI; ++i)
-                        ug[d][i] = Ops<E>::conj(ub[p.block_im_fast ? i + d * BI : i * BD + d]);
+                        ug[d][i] = Ops<E>::conj(to_vec<E>(ub[p.block_im_fast ? i + d * BI : i * BD + d]));
             }
             E xb[BI][KI];
             if (e + 1 < a1) {
@@ -1167,10 +1202,10 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, 
 }
 
 /// Any block / Kronecker sizes: one thread per output element (site, d, column, b)
-template <typename E>
+template <typename EV, typename E>
 __global__ void __launch_bounds__(256) bsr_kron_adj_generic_kernel(const KronAdjArgs p) {
-    const E *__restrict__ v = (const E *)p.v;
-    const E *__restrict__ kron = (const E *)p.kron;
+    const EV *__restrict__ v = (const EV *)p.v;
+    const EV *__restrict__ kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     const long total = p.sites * p.bd * p.ncols * p.kd;
@@ -1186,14 +1221,14 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_generic_kernel(const KronAdj
             const long k = p.ent[e];
             const long I = k / p.nnz, mu = k - I * p.nnz;
             const E *xs = x + (I * p.bi * p.ncols + c) * p.ki;
-            const E *K = kron + mu * p.ki * p.kd;
-            const E *U = v + k * p.bi * p.bd;
+            const EV *K = kron + mu * p.ki * p.kd;
+            const EV *U = v + k * p.bi * p.bd;
             for (int a = 0; a < p.ki; ++a) {
-                const E kk = p.block_im_fast ? K[a + b * p.ki] : K[a * p.kd + b];
+                const E kk = to_vec<E>(p.block_im_fast ? K[a + b * p.ki] : K[a * p.kd + b]);
                 if (!Ops<E>::nonzero(kk)) continue;
                 E s = Ops<E>::zero();
                 for (int i = 0; i < p.bi; ++i) {
-                    const E u = p.block_im_fast ? U[i + d * p.bi] : U[i * p.bd + d];
+                    const E u = to_vec<E>(p.block_im_fast ? U[i + d * p.bi] : U[i * p.bd + d]);
                     s = Ops<E>::fma(Ops<E>::conj(u), xs[i * p.ncols * p.ki + a], s);
                 }
                 acc = Ops<E>::fma(Ops<E>::conj(kk), s, acc);
@@ -1207,7 +1242,8 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_generic_kernel(const KronAdj
 
 constexpr long KRON_LDS_BYTES = 64 * 1024;
 
-template <typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream_t s) {
+/// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
+template <typename EV, typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
     if (g_bsr_tune.kron_adj && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4) {
         const int cpg = (int)std::min<long>(a.ncols, 256);
@@ -1215,23 +1251,25 @@ template <typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream
         const int S = std::min(256 / cpg, stage ? KRON_ADJ_SITES : 256);
         const int nth = (S * cpg + 63) / 64 * 64; // whole waves, at most 256 threads
         const long gx = (a.sites + S - 1) / S, gy = (a.ncols + cpg - 1) / cpg;
+        // (the LDS images are in the vectors' type: a mixed launch widens them at the staging)
         const long lds = (long)((stage ? KRON_ADJ_CHUNK * 9 : 0) + (long)a.nnz * 16) * (long)sizeof(E);
         if (lds <= KRON_LDS_BYTES && gx < (1L << 31) && gy < 65536) {
             g_bsr_tune.last = 15;
             if (stage)
-                hipLaunchKernelGGL((bsr_kron_adj_kernel<E, 3, 3, 4, 4, true>), dim3((unsigned)gx, (unsigned)gy),
+                hipLaunchKernelGGL((bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, true>), dim3((unsigned)gx, (unsigned)gy),
                                    dim3(nth), (size_t)lds, s, a, S, cpg);
             else
-                hipLaunchKernelGGL((bsr_kron_adj_kernel<E, 3, 3, 4, 4, false>), dim3((unsigned)gx, (unsigned)gy),
+                hipLaunchKernelGGL((bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, false>), dim3((unsigned)gx, (unsigned)gy),
                                    dim3(nth), (size_t)lds, s, a, S, cpg);
             SBX_HIP_CHECK(hipGetLastError());
             return;
         }
     }
-    g_bsr_tune.last = 16;
+    // (16 with last_mixed 1 already means bsr_blk_mfma_kernel's mixed form: the mixed launch here is 19)
+    g_bsr_tune.last = std::is_same<EV, E>::value ? 16 : 19;
     const long total = a.sites * a.bd * a.ncols * a.kd;
     const long blocks = std::min((total + 255) / 256, 65536L);
-    hipLaunchKernelGGL((bsr_kron_adj_generic_kernel<E>), dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((bsr_kron_adj_generic_kernel<EV, E>), dim3(blocks), dim3(256), 0, s, a);
     SBX_HIP_CHECK(hipGetLastError());
 }
 
@@ -1260,19 +1298,27 @@ void launch_bsr_kron_adj(const BsrDesc &d, int device) {
     a.alpha_im = d.alpha.im;
     a.add = d.add ? 1 : 0;
     hipStream_t s = get_stream(device);
-    switch (d.t) {
-    case SBX_CDOUBLE: return launch_kron_adj_typed<double2>(a, s);
-    case SBX_CFLOAT: return launch_kron_adj_typed<float2>(a, s);
-    case SBX_DOUBLE: return launch_kron_adj_typed<double>(a, s);
-    case SBX_FLOAT: return launch_kron_adj_typed<float>(a, s);
-    default: throw Error("kron bsr: unsupported type");
-    }
+    // (values' type, vectors' type): the same type, or single-precision values under double vectors
+    if (d.tv == d.t) switch (d.t) {
+        case SBX_CDOUBLE: return launch_kron_adj_typed<double2, double2>(a, s);
+        case SBX_CFLOAT: return launch_kron_adj_typed<float2, float2>(a, s);
+        case SBX_DOUBLE: return launch_kron_adj_typed<double, double>(a, s);
+        case SBX_FLOAT: return launch_kron_adj_typed<float, float>(a, s);
+        default: break;
+        }
+    if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_kron_adj_typed<float2, double2>(a, s);
+    if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_kron_adj_typed<float, double>(a, s);
+    throw Error("kron bsr: unsupported type");
 }
 
-template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
+/// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
+template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
-    const long row_bytes = (long)a.nnz * (a.bi * a.bd * sizeof(E) + sizeof(int));
-    if constexpr (std::is_same<E, double2>::value) {
+    constexpr bool same = std::is_same<EV, E>::value;
+    // (bsr_kron_lds_kernel's LDS image holds the values as stored)
+    const long row_bytes = (long)a.nnz * (a.bi * a.bd * sizeof(EV) + sizeof(int));
+    // the spin-first kernels read their tables of doubles: same-type products only
+    if constexpr (std::is_same<E, double2>::value && same) {
         if (g_bsr_tune.kron_spin == 2 && a.xtab && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 &&
             a.nnz >= 1 && a.ncols >= g_bsr_tune.kron_spin_min_cols && a.x_rows * 4 * a.ncols < (1L << 31) &&
             a.block_rows * a.ncols + 1024 < (1L << 31)) {
@@ -1299,8 +1345,21 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
                 return;
             }
         }
+    }
+    if constexpr (std::is_same<E, double2>::value) {
+        // complex<float> values (bsr.kron_mixed) take the same conditions and the same column
+        // bound, kron_mfma_min_cols (8), as complex<double> ones.  Measured against the mixed VALU
+        // form (bsr_kron_lds_kernel<float2, double2>; tools/studies/kron_mixed.py,
+        // profiles/kron_mixed_measure.txt, 16^4 and 16^3 x 64): the matrix-core forms are 1.35-1.9x
+        // faster at 8, 12, 16, 32 and 64 columns, the round-to-round spreads below 2 % of either
+        // time -- so from 8 columns they are taken.  They were faster at 1 and 4 columns too
+        // (1.2x, 2.0x: kron_mfma_min_cols 1 takes them there); the default bound is not lowered
+        // for one pair of types alone, and 2, 3 and 5-7 columns (5 and 7 do not pack) are not
+        // measured.
+        // (the 2 GiB bound: the colour run's LDS-DMA buffer offsets; the mixed form stages the run
+        // by plain loads with 64-bit addresses)
         if (g_bsr_tune.kron_mfma && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 && a.nnz == 9 &&
-            a.ncols >= g_bsr_tune.kron_mfma_min_cols && a.block_rows * 81L * 16 < (1L << 31)) {
+            a.ncols >= g_bsr_tune.kron_mfma_min_cols && (!same || a.block_rows * 81L * 16 < (1L << 31))) {
             // packed slots: W waves of 16 (row, column) slots hold RW = 16 W / n whole rows
             int wpk = 0;
             for (int wv = 4; wv >= 1 && g_bsr_tune.kron_pack; --wv)
@@ -1316,9 +1375,11 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
                     // LDS: rw rows of 81 color values, rounded up to whole DMA passes of the
                     // workgroup (the lanes past the run write zeros)
                     const int nth = 64 * wpk;
-                    const size_t lds_cb = (size_t)((rw * 81 + nth - 1) / nth * nth) * 16;
+                    // (mixed: the same count of 8-byte values, a multiple of 16 bytes as nth is of 64;
+                    // staged by plain loads bounded by the run: no DMA pass to size for)
+                    const size_t lds_cb = (size_t)((rw * 81 + nth - 1) / nth * nth) * sizeof(EV);
                     // the DMA loop: passes u < ceil(nrows * 81 / nth), nrows <= rw
-                    check_dma_lds("bsr_kron_mfma_packed_kernel", lds_cb, (rw * 81L + nth - 1) / nth, nth);
+                    if (same) check_dma_lds("bsr_kron_mfma_packed_kernel", lds_cb, (rw * 81L + nth - 1) / nth, nth);
                     // x by LDS-DMA: a ring of 2 x 3 KB per wave after the color blocks (lds_cb is
                     // a multiple of 16); 32-bit buffer offsets
                     const int xl = std::max(a.block_rows * 12L, a.x_rows * 4L) * a.ncols * 16 < (1L << 31)
@@ -1332,11 +1393,11 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
                     auto go = [&](auto kern) {
                         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpk), lds_bytes, s, a, rw, (int)lds_cb);
                     };
-                    if (xl == 1) go(bsr_kron_mfma_packed_kernel<9, true, 1>);
-                    else if (xl == 2) go(bsr_kron_mfma_packed_kernel<9, true, 2>);
-                    else if (xl == 3) go(bsr_kron_mfma_packed_kernel<9, true, 3>);
+                    if (xl == 1) go(bsr_kron_mfma_packed_kernel<9, true, 1, EV>);
+                    else if (xl == 2) go(bsr_kron_mfma_packed_kernel<9, true, 2, EV>);
+                    else if (xl == 3) go(bsr_kron_mfma_packed_kernel<9, true, 3, EV>);
                     else
-                        hipLaunchKernelGGL((bsr_kron_mfma_packed_kernel<9, true>), dim3((unsigned)blocks),
+                        hipLaunchKernelGGL((bsr_kron_mfma_packed_kernel<9, true, 0, EV>), dim3((unsigned)blocks),
                                            dim3(64 * wpk), lds_bytes, s, a, rw, (int)lds_cb);
                     SBX_HIP_CHECK(hipGetLastError());
                     return;
@@ -1352,11 +1413,11 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
                 auto go = [&](auto kern) {
                     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)ngroups);
                 };
-                if (xl == 1) go(bsr_kron_mfma_kernel<9, false, 1>);
-                else if (xl == 2) go(bsr_kron_mfma_kernel<9, false, 2>);
-                else if (xl == 3) go(bsr_kron_mfma_kernel<9, false, 3>);
+                if (xl == 1) go(bsr_kron_mfma_kernel<9, false, 1, EV>);
+                else if (xl == 2) go(bsr_kron_mfma_kernel<9, false, 2, EV>);
+                else if (xl == 3) go(bsr_kron_mfma_kernel<9, false, 3, EV>);
                 else
-                    hipLaunchKernelGGL((bsr_kron_mfma_kernel<9, false>), dim3((unsigned)blocks), dim3(256), 0,
+                    hipLaunchKernelGGL((bsr_kron_mfma_kernel<9, false, 0, EV>), dim3((unsigned)blocks), dim3(256), 0,
                                        s, a, (int)ngroups);
                 SBX_HIP_CHECK(hipGetLastError());
                 return;
@@ -1368,16 +1429,16 @@ template <typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
         const int cpg = (int)std::min<long>(a.ncols, 256);
         const int S = 256 / cpg;
         const dim3 grid((unsigned)((a.block_rows + S - 1) / S), (unsigned)((a.ncols + cpg - 1) / cpg));
-        hipLaunchKernelGGL((bsr_kron_lds_kernel<E, 3, 3, 4, 4, 9>), grid, dim3(256),
+        hipLaunchKernelGGL((bsr_kron_lds_kernel<EV, E, 3, 3, 4, 4, 9>), grid, dim3(256),
                            (size_t)(row_bytes * S), s, a, S, cpg);
     } else if (a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4) {
         const long total = a.block_rows * a.ncols;
         const long blocks = std::min((total + 255) / 256, 65536L);
-        hipLaunchKernelGGL((bsr_kron_kernel<E, 3, 3, 4, 4>), dim3(blocks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((bsr_kron_kernel<EV, E, 3, 3, 4, 4>), dim3(blocks), dim3(256), 0, s, a);
     } else {
         const long total = a.block_rows * a.bi * a.ncols * a.ki;
         const long blocks = std::min((total + 255) / 256, 65536L);
-        hipLaunchKernelGGL((bsr_kron_generic_kernel<E>), dim3(blocks), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((bsr_kron_generic_kernel<EV, E>), dim3(blocks), dim3(256), 0, s, a);
     }
     SBX_HIP_CHECK(hipGetLastError());
 }
@@ -1414,15 +1475,20 @@ void launch_bsr_kron(const BsrDesc &d, int device) {
     // bounded by x's extent, not y's
     a.x_rows = d.x_rows > 0 ? d.x_rows : d.block_rows * d.bd;
     a.perm = g_bsr_tune.kron_order ? d.kron_perm : nullptr;
-    a.ktab = d.kron_terms;
-    a.xtab = d.kron_xor;
-    switch (d.t) {
-    case SBX_CDOUBLE: return launch_kron_typed<double2>(a, s);
-    case SBX_CFLOAT: return launch_kron_typed<float2>(a, s);
-    case SBX_DOUBLE: return launch_kron_typed<double>(a, s);
-    case SBX_FLOAT: return launch_kron_typed<float>(a, s);
-    default: throw Error("kron bsr: unsupported type");
-    }
+    // (the spin-first tables: null on a mixed launch, whose operator never builds them)
+    a.ktab = d.tv == d.t ? d.kron_terms : nullptr;
+    a.xtab = d.tv == d.t ? d.kron_xor : nullptr;
+    // (values' type, vectors' type): the same type, or single-precision values under double vectors
+    if (d.tv == d.t) switch (d.t) {
+        case SBX_CDOUBLE: return launch_kron_typed<double2, double2>(a, s);
+        case SBX_CFLOAT: return launch_kron_typed<float2, float2>(a, s);
+        case SBX_DOUBLE: return launch_kron_typed<double, double>(a, s);
+        case SBX_FLOAT: return launch_kron_typed<float, float>(a, s);
+        default: break;
+        }
+    if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_kron_typed<float2, double2>(a, s);
+    if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_kron_typed<float, double>(a, s);
+    throw Error("kron bsr: unsupported type");
 }
 
 } // namespace sbx

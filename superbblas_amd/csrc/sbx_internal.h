@@ -372,6 +372,13 @@ struct BsrTune {
                          ///< the values as A does (last_kernel 17 / 18; 3x3 and 12x12 operators
                          ///< give up their LDS-DMA kernels for it).  Kronecker operators ignore it
                          ///< (always in place)
+    int kron_mixed = 0; ///< operators of create_kron_bsr kept in float / complex<float> (colour blocks and
+                        ///< spin matrices) applied to double / complex<double> vectors, read at each
+                        ///< bsr_krylov call: 0 = refused (any type difference on a Kronecker operator
+                        ///< throws), 1 = admitted, A x and A^H x: the values are read in place and
+                        ///< widened at the load, everything else is FP64 (the kernels of
+                        ///< kernels_bsr_kron.hip with a value type beside the vector type; the
+                        ///< spin-first kernels, kron_spin 1 / 2, are not taken)
     /// read-back ("bsr.adj_copy_bytes"): bytes held by the value copies of transposed operators,
     /// process-wide (grows when a copy is made, shrinks when its operator is destroyed)
     std::atomic<long long> adj_copy_bytes{0};
@@ -384,12 +391,15 @@ struct BsrTune {
     /// 13 site tiles of 8 sites and 16 columns (3x3), 14 dense blocks of blk_min and more on MFMA
     /// (bsr_blk_mfma_kernel), 15 Kronecker adjoint, a thread per (domain site, column)
     /// (bsr_kron_adj_kernel), 16 Kronecker adjoint, a thread per output element -- or, with
-    /// last_mixed 1 (Kronecker operators are never mixed), dense blocks with single-precision
-    /// values and double-precision vectors on MFMA (bsr_blk_mfma_kernel, values narrower),
+    /// last_mixed 1 (a mixed Kronecker adjoint on that kernel reports 19), dense blocks with
+    /// single-precision values and double-precision vectors on MFMA (bsr_blk_mfma_kernel, values
+    /// narrower),
     /// 17 the in-place adjoint of dense blocks on MFMA (bsr_blk_mfma_kernel, ADJ), 18 the in-place
-    /// adjoint, a thread per output element (bsr_kernel, ADJ),
+    /// adjoint, a thread per output element (bsr_kernel, ADJ), 19 Kronecker adjoint, a thread per
+    /// output element, single-precision values under double-precision vectors (kron_mixed),
     /// 0 another kernel.  7, 8, 10 and 11 with last_mixed 1: the same 12x12 kernels reading values of
-    /// the narrower type (mixed12_min_cols, mixed12_pack)
+    /// the narrower type (mixed12_min_cols, mixed12_pack); 5, 6 and 15 with last_mixed 1: the same
+    /// Kronecker kernels reading single-precision values (kron_mixed)
     std::atomic<int> last{0};
     /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type
     /// than its vectors, else 0
