@@ -16,6 +16,7 @@
 //    blocks from LDS (broadcast across the rhs lanes) and x from global memory (contiguous along
 //    the rhs for row-major x).
 #include "elem_ops.h"
+#include "kernel_util.h"
 #include "sbx_internal.h"
 
 #include <algorithm>
@@ -138,9 +139,7 @@ __global__ void __launch_bounds__(256) bsr_ell_kernel(const BsrArgs p, int nnz, 
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     // consecutive chunks of block rows on one XCD: neighbouring sites share x rows in its L2
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int chunk = xcd_chunk(blockIdx.x, gridDim.x);
     const long row0 = (long)chunk * rb;
     const int nrows = (int)min((long)rb, p.block_rows - row0);
     // 1) stream the chunk's nonzero blocks (contiguous in the ELL value array) and block
@@ -237,50 +236,6 @@ __global__ void __launch_bounds__(256) bsr_ell_kernel(const BsrArgs p, int nnz, 
 // from global memory: lane l reads A_ij[l&15][k+(l>>4)] and x[d_j+k+(l>>4)][col0+(l&15)]
 // (contiguous along the rhs for row-major x); out-of-range rows, columns and skipped blocks
 // (-1 columns) are clamped loads replaced by zero, so the loop has no divergent branches.
-__device__ __forceinline__ unsigned lds_u32(const void *p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void *)p;
-}
-
-/// s_waitcnt vmcnt(n) for an n the unrolled caller knows at compile time (folds to one wait)
-__device__ __forceinline__ void wait_vmcnt_n(int n) {
-    switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned off, unsigned dst, int nt = 0) {
-    // inline asm: hipcc does not order its ds_reads against an LDS-DMA it cannot see; the kernel
-    // retires the DMA with an explicit vmcnt(0) before its barrier.  nt (a uniform kernel
-    // argument, so a scalar branch): the streaming policy for data read once (the values)
-    if (nt)
-        asm volatile("s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %0, %2, 0 offen nt lds"
-                     :
-                     : "v"(off), "s"(dst), "s"(rs)
-                     : "memory", "m0");
-    else
-        asm volatile("s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                     :
-                     : "v"(off), "s"(dst), "s"(rs)
-                     : "memory", "m0");
-}
-
 // (BsrNarrow / BsrStored, an element of a narrower operator as it lies in memory: elem_ops.h)
 
 template <typename R, bool CPLX> struct BsrMfmaElem;
@@ -575,20 +530,7 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
                 if (g < SLOT) {
                     const char *src = g < (unsigned)(ABLK * EVS) ? vrow + g : xrow + (g - ABLK * EVS);
                     // nt on the instructions that carry values only (x rows are reused)
-                    if ((p.nt & 1) && (q + 1) * 1024 <= ABLK * EVS)
-                        asm volatile("s_mov_b32 m0, %1\n\t"
-                                     "s_nop 0\n\t"
-                                     "global_load_lds_dwordx4 %0, off nt"
-                                     :
-                                     : "v"(src), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)q * 1024u))
-                                     : "memory", "m0");
-                    else
-                        asm volatile("s_mov_b32 m0, %1\n\t"
-                                     "s_nop 0\n\t"
-                                     "global_load_lds_dwordx4 %0, off"
-                                     :
-                                     : "v"(src), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)q * 1024u))
-                                     : "memory", "m0");
+                    dma16_lane(src, base + (unsigned)q * 1024u, (p.nt & 1) && (q + 1) * 1024 <= ABLK * EVS);
                 }
             }
         } else {
@@ -616,7 +558,7 @@ __global__ void __launch_bounds__(256) bsr_mfma_dma_kernel(const BsrArgs p, unsi
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (k + PD < NNZ) issue(k + PD);
         // block k landed: the NI instructions of each later block issued so far may stay in flight
-        wait_vmcnt_n(NI * (NNZ - 1 - k < PD ? NNZ - 1 - k : PD));
+        wait_vmcnt(NI * (NNZ - 1 - k < PD ? NNZ - 1 - k : PD));
         if (dj[k] < 0) continue;
         const EV *sa = (const EV *)(smem + (slot0 - lds_u32(smem)) + (k % (PD + 1)) * SLOT);
         const E *sx = (const E *)(sa + (PK > 0 ? ABLK : NA * 1024 / EVS));
@@ -731,7 +673,7 @@ bool launch_bsr_mfma_dma_mixed(const BsrArgs &a, bool yrow, hipStream_t s) {
     constexpr int NA = (BI * BD * EVS + 1023) / 1024, NX = (BD * 16 * ES + 1023) / 1024;
     constexpr int PKMIN = (BI * BD * EVS + BD * ES + 1023) / 1024, PKMAX = (BI * BD * EVS + BD * 16 * ES + 1023) / 1024;
     static_assert((BI * BD * EVS) % 16 == 0, "a value block is whole 16-byte pieces");
-    static_assert(PKMAX <= 5, "wait_vmcnt_n's counts");
+    static_assert(PKMAX <= 5, "wait_vmcnt's counts");
     const long v_bytes = a.block_rows * NNZ * (long)BI * BD * EVS, x_bytes = a.x_rows * a.ldx * (long)ES;
     if (a.x_rows <= 0 || x_bytes >= (1L << 31)) return false;
     const long blocks = (a.block_rows + 3) / 4;
@@ -851,12 +793,8 @@ __global__ void __launch_bounds__(NT) bsr_ell9_kernel(const BsrArgs p, int rb) {
     const E *__restrict__ v = (const E *)p.v;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
     // the XCD's range of chunks visited as p.ilv interleaved parts (bsr_ell9_split_kernel)
-    const int cnt = xcd < r8 ? q8 + 1 : q8, qx = bid >> 3, npart = cnt / p.ilv;
-    const int loc = (p.ilv > 1 && qx < npart * p.ilv) ? (qx % p.ilv) * npart + qx / p.ilv : qx;
-    const int chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    const int chunk = xcd_chunk(blockIdx.x, gridDim.x, p.ilv);
     const long row0 = (long)chunk * rb;
     const int nrows = (int)min((long)rb, p.block_rows - row0);
     const long ngroups = (p.ncols + G - 1) / G;
@@ -902,7 +840,7 @@ __global__ void __launch_bounds__(NT) bsr_ell9_kernel(const BsrArgs p, int rb) {
         for (int u = 0; u * NT < nv; ++u) {
             const int e = u * NT + (int)threadIdx.x;
             const unsigned off = e < nv ? (unsigned)((vbase + e) * 16) : 0x80000000u;
-            dma16(rs, off, __builtin_amdgcn_readfirstlane(base + (unsigned)(u * NT) * 16u), p.nt & 2);
+            dma16(rs, off, base + (unsigned)(u * NT) * 16u, p.nt & 2);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
@@ -977,23 +915,6 @@ struct TileArgs {
     int umax;
 };
 
-__device__ __forceinline__ void dma16_lane(const void *src, unsigned m0, bool nt) {
-    if (nt)
-        asm volatile("s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, off nt"
-                     :
-                     : "v"(src), "s"(m0)
-                     : "memory", "m0");
-    else
-        asm volatile("s_mov_b32 m0, %1\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, off"
-                     :
-                     : "v"(src), "s"(m0)
-                     : "memory", "m0");
-}
-
 // the x DMA passes of a slice: umax * 3 * NS pieces over TT * 3 * NS lanes (the launcher bounds umax)
 template <int TT, int NS> struct TileForm {
     static constexpr int NT = TT * 3 * NS;
@@ -1013,9 +934,7 @@ __global__ void __launch_bounds__(TT * 3 * NS) bsr_ell9_tile_kernel(const BsrArg
     E *xs = vals + VP;
     const int tid = threadIdx.x, w = tid >> 6;
     // XCD-contiguous ranges of tiles: neighbouring tiles share halo rows in that XCD's L2
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int chunk = xcd_chunk(blockIdx.x, gridDim.x);
     if (chunk >= nchunks) return;
     const int umax = t.umax, XP = umax * 3 * NS; // x pieces of a slice
     const int *rows = t.rows + (long)chunk * TT;
@@ -1029,7 +948,7 @@ __global__ void __launch_bounds__(TT * 3 * NS) bsr_ell9_tile_kernel(const BsrArg
         if (L < VP) {
             const int s = L / 81, r = rows[s];
             dma16_lane(v + (long)(r < 0 ? 0 : r) * 81 + (L - s * 81),
-                       __builtin_amdgcn_readfirstlane(vbase + (unsigned)(u * NT + w * 64) * 16u), (p.nt & 2) != 0);
+                       vbase + (unsigned)(u * NT + w * 64) * 16u, (p.nt & 2) != 0);
         }
     }
     // this lane's x pieces (pass u: distinct row pu, colour pd, column pe), the same every slice
@@ -1048,7 +967,7 @@ __global__ void __launch_bounds__(TT * 3 * NS) bsr_ell9_tile_kernel(const BsrArg
         for (int u = 0; u < MAXP; ++u) {
             const int L = u * NT + tid;
             if (u * NT < XP && L < XP)
-                dma16_lane(x + src[u] + q * NS, __builtin_amdgcn_readfirstlane(xbase + (unsigned)(u * NT + w * 64) * 16u), false);
+                dma16_lane(x + src[u] + q * NS, xbase + (unsigned)(u * NT + w * 64) * 16u, false);
         }
     };
     // this thread's output and its nine slots
@@ -1166,9 +1085,7 @@ __global__ void __launch_bounds__(256) bsr_ell9_row_kernel(const BsrArgs p, unsi
     const E *__restrict__ v = (const E *)p.v;
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const long chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const long chunk = xcd_chunk(blockIdx.x, gridDim.x);
     const int tid = threadIdx.x, rl = tid / NNZ, j = tid - rl * NNZ;
     const long row = chunk * RW + rl;
     const int ncols = (int)p.ncols;
@@ -1198,7 +1115,7 @@ __global__ void __launch_bounds__(256) bsr_ell9_row_kernel(const BsrArgs p, unsi
         for (int u = 0; u < (NV + 255) / 256; ++u) {
             const unsigned e = (unsigned)(u * 256 + tid);
             const unsigned off = e < (unsigned)NV ? v0 + e * 16u : 0x80000000u;
-            dma16(rs, off, __builtin_amdgcn_readfirstlane(base + (unsigned)u * 4096u), p.nt & 8);
+            dma16(rs, off, base + (unsigned)u * 4096u, p.nt & 8);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1304,14 +1221,10 @@ __global__ void __launch_bounds__(512) bsr_ell9_split_kernel(const BsrArgs p, co
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double2 *vals = (double2 *)smem;
     const int nth = blockDim.x, tid = threadIdx.x;
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
     // the XCD's contiguous range of chunks, its parts interleaved: with ilv = 2 the two halves
     // (on the 16^4 lattice: the XCD's two x slices) are visited together, so a site's +-x
     // neighbour rows are read while the other half still holds them in this XCD's L2
-    const int cnt = xcd < r8 ? q8 + 1 : q8, q = bid >> 3, npart = cnt / s.ilv;
-    const int loc = (s.ilv > 1 && q < npart * s.ilv) ? (q % s.ilv) * npart + q / s.ilv : q;
-    const long chunk = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
+    const long chunk = xcd_chunk(blockIdx.x, gridDim.x, s.ilv);
     const long row0 = chunk * s.rw;
     const int nrows = (int)min((long)s.rw, p.block_rows - row0);
     const int nv = nrows * NNZ * 9, nvp = (s.rw * NNZ * 9 + nth - 1) / nth * nth;
@@ -1354,7 +1267,7 @@ __global__ void __launch_bounds__(512) bsr_ell9_split_kernel(const BsrArgs p, co
         for (int u = 0; u * nth < nv; ++u) {
             const int e = u * nth + tid;
             const unsigned off = e < nv ? v0 + (unsigned)e * 16u : 0x80000000u;
-            dma16(rs, off, __builtin_amdgcn_readfirstlane(base + (unsigned)(u * nth) * 16u), p.nt & 4);
+            dma16(rs, off, base + (unsigned)(u * nth) * 16u, p.nt & 4);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }

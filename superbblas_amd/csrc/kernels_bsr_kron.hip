@@ -12,6 +12,7 @@
 // and the spin matrix K_mu is wave-uniform (scalar loads; zero entries -- half of a Wilson
 // projector -- are skipped with a scalar branch).
 #include "elem_ops.h"
+#include "kernel_util.h"
 #include "sbx_internal.h"
 
 #include <algorithm>
@@ -39,6 +40,20 @@ struct KronArgs {
     const void *ktab; ///< ... the spin matrices' rows as two terms (bsr.cpp build_kron_terms)
     const void *xtab; ///< ... as diagonal + XOR partner (nullptr: not of that form)
 };
+
+/// The epilogue of a lane that owns NI x NA outputs of y (., i, n, a) at column c, ys = &y(., 0, c, 0):
+/// y(i, a) = alpha acc(i, a) [+ y(i, a)], acc(i, a) the lane's sum as an E
+template <typename E, int NI, int NA, typename Acc>
+__device__ __forceinline__ void store_outputs(E *ys, long n, double alpha_re, double alpha_im, int add, Acc acc) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            E o = Ops<E>::scale(acc(i, a), alpha_re, alpha_im);
+            if (add) o = Ops<E>::add(o, ys[i * n * NA + a]);
+            ys[i * n * NA + a] = o;
+        }
+}
 
 // Mixed precision (bsr.kron_mixed): every kernel of this file but the spin-first ones has a value
 // type EV beside the vector type E -- EV = E, or float / float2 under double / double2.  The
@@ -94,54 +109,10 @@ __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
                     for (int a = 0; a < KI; ++a) acc[i][a] = Ops<E>::fma(u, xk[d][a], acc[i][a]);
                 }
         }
-        E *ys = y + (r * BI * p.ncols + c) * KI;
-#pragma unroll
-        for (int i = 0; i < BI; ++i)
-#pragma unroll
-            for (int a = 0; a < KI; ++a) {
-                E o = Ops<E>::scale(acc[i][a], p.alpha_re, p.alpha_im);
-                if (p.add) o = Ops<E>::add(o, ys[i * p.ncols * KI + a]);
-                ys[i * p.ncols * KI + a] = o;
-            }
+        store_outputs<E, BI, KI>(y + (r * BI * p.ncols + c) * KI, p.ncols, p.alpha_re, p.alpha_im, p.add,
+                                 [&](int i, int a) { return acc[i][a]; });
     }
 }
-
-/// s_waitcnt vmcnt(n) for an n the unrolled caller knows at compile time (folds to one wait)
-__device__ __forceinline__ void wait_vmcnt(int n) {
-    switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    }
-}
-
-/// Wave-uniform element load through the constant address space (scalar loads into SGPRs)
-template <typename R> using ConstPtr = const __attribute__((address_space(4))) R *;
-template <typename E> struct Uniform {
-    static __device__ __forceinline__ E load(const E *p, long i) {
-        return ((ConstPtr<E>)p)[i];
-    }
-};
-template <> struct Uniform<double2> {
-    static __device__ __forceinline__ double2 load(const double2 *p, long i) {
-        const ConstPtr<double> q = (ConstPtr<double>)p;
-        return double2{q[2 * i], q[2 * i + 1]};
-    }
-};
-template <> struct Uniform<float2> {
-    static __device__ __forceinline__ float2 load(const float2 *p, long i) {
-        const ConstPtr<float> q = (ConstPtr<float>)p;
-        return float2{q[2 * i], q[2 * i + 1]};
-    }
-};
 
 /// Many rhs columns: a workgroup owns `S` consecutive block rows x up to 256 columns; the color
 /// blocks of its rows (S * NNZ * BI * BD values, contiguous in memory) and their domain sites are
@@ -162,9 +133,7 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
     const E *__restrict__ x = (const E *)p.x;
     E *__restrict__ y = (E *)p.y;
     // consecutive chunks of block rows on one XCD: neighbouring sites share x lines in its L2
-    const int nwg = gridDim.x * gridDim.y, bid = blockIdx.x + blockIdx.y * gridDim.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int wg = xcd_chunk(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
     const int gx = wg % gridDim.x, gy = wg / gridDim.x;
     const long r0 = (long)gx * S;
     const int nrows = (int)std::min<long>(S, p.block_rows - r0);
@@ -236,15 +205,8 @@ __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int
                 for (int b = 0; b < KD; ++b) xa[d][b] = xb[d][b];
         }
     }
-    E *ys = y + (r * BI * p.ncols + c) * KI;
-#pragma unroll
-    for (int i = 0; i < BI; ++i)
-#pragma unroll
-        for (int a = 0; a < KI; ++a) {
-            E o = Ops<E>::scale(acc[i][a], p.alpha_re, p.alpha_im);
-            if (p.add) o = Ops<E>::add(o, ys[i * p.ncols * KI + a]);
-            ys[i * p.ncols * KI + a] = o;
-        }
+    store_outputs<E, BI, KI>(y + (r * BI * p.ncols + c) * KI, p.ncols, p.alpha_re, p.alpha_im, p.add,
+                             [&](int i, int a) { return acc[i][a]; });
 }
 
 /// Any block / Kronecker sizes: one thread per output element (block row, i, column, a)
@@ -285,32 +247,60 @@ __global__ void __launch_bounds__(256) bsr_kron_generic_kernel(const KronArgs p)
     }
 }
 
-// complex<double>, 3x3 color blocks, 4x4 spin matrices, from 8 rhs columns: one wave per (block
-// row, group of 16 rhs columns), lane l = 16 b + q owning spin b of column q of the group.
-//  * color on the VALU: T_mu(i, b, q) = sum_d U_mu(i, d) x(J_mu, d, q, b) -- the row's color
-//    blocks and block columns are wave-uniform (scalar loads, SGPR operands), the x loads of a
-//    neighbour are lane-linear 16-byte pieces (1 KB per wave instruction at 16 columns);
+// complex<double> vectors, 3x3 color blocks, 4x4 spin matrices, from 8 rhs columns, on the matrix
+// cores: bsr_kron_mfma_kernel (form 5) and bsr_kron_mfma_packed_kernel (form 6).  A wave owns 16
+// column slots of a block row (form 6: of several rows), lane l = 16 b + q owning spin b of slot q.
+//  * color on the VALU: T_mu(i, b, q) = sum_d U_mu(i, d) x(J_mu, d, q, b) -- the color blocks of
+//    the workgroup's rows are one contiguous run of the value array, staged in LDS once and
+//    read back as broadcasts;
 //  * spin on the matrix cores: acc(a, i, q) += sum_b K_mu(a, b) T_mu(i, b, q) is a 4x4x4 product
-//    per group of 4 columns, i.e. v_mfma_f64_4x4x4_4b_f64 with A = K_mu (lane 16 b + 4 g + a, the
+//    per group of 4 slots, i.e. v_mfma_f64_4x4x4_4b_f64 with A = K_mu (lane 16 b + 4 g + a, the
 //    same in all 4 blocks), B = T (lane 16 b + q) and C = acc (lane 16 a + q) -- the lane maps
 //    measured by tools/mfma_small.hip -- 4 real products per complex one (the BLAS rounding);
-//  * the next neighbour's x is loaded while the current one is applied; 4 rows per workgroup,
-//    an XCD's rows visited as two interleaved halves (its ilv form of the 3x3 kernels).
-// The previous kernel (one thread per (row, column) owning all 12 outputs) ran at 256 VGPRs:
-// 2 waves per SIMD.
-// XL > 0: x staged by LDS-DMA in whole 64-B spin pieces, XL neighbours ahead (see
-// bsr_kron_mfma_packed_kernel)
+//  * XL = 0: the next neighbour's x is loaded into VGPRs while the current one is applied (per
+//    lane: 3 loads of 16 bytes, lane-linear over the columns of one spin);
+//  * XL > 0: the neighbours' x pieces staged by LDS-DMA instead.  The MFMA's B operand wants lane
+//    16 b + q = spin b of slot q, but spin is the fastest index of x in memory, so a 16-lane
+//    quarter of such a load touches 16 pieces 64 B apart (8 cache lines; 32 TA/TCP accesses per
+//    1-KB instruction against 8 for a linear one, and TA/TD busy 85-92 %).  The DMA instead moves
+//    each slot's 4 spins as one 64-B piece (lane l: slot l / 4), writes them lane-linear into the
+//    wave's ring (XL neighbours ahead, 3 KB per neighbour: deeper prefetch costs LDS, not VGPRs),
+//    and the B lanes read them back with the spins rotated (position 4 q + (b + q / 2 + q / 8)
+//    mod 4: the 16-B granules of any 8 or 16 lanes reading together fall on distinct banks).  The
+//    spin matrices then sit in LDS too: no vector-memory load in the main loop, where the
+//    compiler's own vmcnt waits (blind to the DMAs) would drain the x ring;
+//  * p.ylds (XL > 0): y leaves through the same ring, each slot's 4 spins one 64-B run.
 // EV = float2 (complex<float> values under complex<double> vectors, bsr.kron_mixed): only the
 // colour run and the spin operand's source change.  The run sits in LDS as stored (8-byte values,
 // half the LDS) and is widened at the LDS read; it is staged by plain 8-byte loads and LDS
 // writes, not by LDS-DMA: the DMA moves 16-byte pieces, and a run of 8-byte values starts at
-// rlo * 81 * 8 bytes of a tensor that is itself only 8-byte aligned -- no multiple of 16 for an odd
-// rlo (40 columns: ngroups 3, rlo = floor(4 wgi / 3)) or an odd base.  The loads are bounded by
-// the run (e < nu), so nothing past the value array is read, whatever its alignment or length;
-// at most two loads a lane, once per workgroup, before the x ring starts.  The spin matrices are
-// widened where the ks image is filled (XL) or where they are loaded.
-template <int NNZ, bool kpf = false, int XL = 0, typename EV = double2>
-__global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, int ngroups) {
+// row * 81 * 8 bytes of a tensor that is itself only 8-byte aligned -- no multiple of 16 for an odd
+// first row (form 5 at 40 columns: ngroups 3, first row floor(4 wgi / 3)) or an odd base (form 6:
+// the first row is even, the base need not be).  The loads are bounded by the run (e < nu), so
+// nothing past the value array is read, whatever its alignment or length; at most two loads a
+// lane, once per workgroup, before the x ring starts.  The spin matrices are widened where the
+// ks image is filled (XL) or where they are loaded.
+//
+// One kernel (bsr_kron_mfma_form_kernel), two maps from lanes to (row, column) (PACK: false is
+// bsr_kron_mfma_kernel, true bsr_kron_mfma_packed_kernel), everything else once -- and in the
+// kernel's own text, not in helper functions: the compiler simplifies a helper before it inlines
+// it, and this loop unrolled inside one, with the lane's data behind references, compiled to
+// 90-190 instructions more and to other register counts.
+//  * !PACK (form 5): 4 waves, wave w of workgroup wgi takes task 4 wgi + w of the (block row,
+//    group of 16 columns) tasks, row-major over the a0 = ngroups groups.  The row is
+//    wave-uniform, its block columns scalar loads where they are used; static LDS.
+//  * PACK (form 6), rhs counts below 16 that divide 16 W (W <= 4 waves): the workgroup's 16 W
+//    slots are the (row, column) pairs of its a0 = RW = 16 W / n consecutive block rows, so no
+//    lane idles (at n = 12 one wave per row left 4 of 16 slots empty: 25 % of the VALU and MFMA
+//    work).  The row is per lane: its block columns, and those of the DMA slot's row, are loaded
+//    into registers up front.  Dynamic LDS: the color blocks of RW rows, from byte a1 the W
+//    rings, then the spin matrices (the launcher sizes all three).
+// XCD-contiguous workgroups, the XCD's range visited as two interleaved halves (the ilv form of
+// the 3x3 kernels).  The kernel before these (one thread per (row, column) owning all 12 outputs)
+// ran at 256 VGPRs: 2 waves per SIMD.
+template <bool PACK, int NNZ, bool kpf = false, int XL = 0, typename EV = double2>
+__global__ void __launch_bounds__(256) bsr_kron_mfma_form_kernel(const KronArgs p, int a0, int a1) {
+    constexpr int NS = XL + 1;
     typedef double2 E;
     constexpr bool same = std::is_same<EV, E>::value;
     typedef typename BsrStored<EV, E>::type SV; // a value as stored: reading it as E widens
@@ -318,105 +308,145 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
     E *__restrict__ y = (E *)p.y;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // XCD-contiguous chunks of 4 block rows, the XCD's range visited as two interleaved halves
-    const long nchunk = (p.block_rows + 3) / 4;
-    const int bid = blockIdx.x, nwg = gridDim.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int cnt = xcd < r8 ? q8 + 1 : q8, qx = bid >> 3, npart = cnt / 2;
-    const int loc = (npart > 0 && qx < npart * 2) ? (qx % 2) * npart + qx / 2 : qx;
-    const long wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    const long task = wgi * 4 + w; // (row chunk, column group) tasks: row-major over groups
-    const long r = task / ngroups;
-    const int cg = (int)(task - r * ngroups);
-    // the color blocks of the workgroup's rows (rows of a task group are consecutive: one
-    // contiguous run) into LDS by one DMA pass, read back as broadcasts
-    // (rounded up to whole DMA passes of 256 lanes: the lanes past the run write zeros)
-    __shared__ __attribute__((aligned(16))) EV us[(4 * NNZ * 9 + 255) / 256 * 256];
-    // a workgroup's 4 tasks span at most 4 rows: nu <= 4 * NNZ * 9, every pass of 256 lanes fits
-    static_assert(sizeof(us) / sizeof(EV) >= (4 * NNZ * 9 + 255) / 256 * 256, "LDS sizing");
-    // XL: the spin matrices in LDS -- no vector-memory load in the main loop, where the
-    // compiler's own vmcnt waits (blind to the DMAs) would drain the x ring
-    __shared__ __attribute__((aligned(16))) E ks[XL ? NNZ * 16 : 1];
-    if constexpr (XL > 0)
-        for (int e = (int)threadIdx.x; e < NNZ * 16; e += 256) ks[e] = ((const SV *)p.kron)[e];
-    {
-        const long rlo = (wgi * 4) / ngroups, rhi = min((wgi * 4 + 3) / ngroups, p.block_rows - 1);
-        const int nu = (int)(rhi - rlo + 1) * NNZ * 9; // <= 4 * NNZ * 9 <= the elements of us
-        if constexpr (!same) {
-            const EV *__restrict__ src = (const EV *)p.v + rlo * NNZ * 9;
-            for (int e = (int)threadIdx.x; e < nu; e += 256) us[e] = src[e];
-        } else {
-            // (launcher: the value array is below 2 GiB)
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
-            const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)us +
-                                  (unsigned)w * 1024u;
-            for (int u = 0; u * 256 < nu; ++u) {
-                const int e = u * 256 + (int)threadIdx.x;
-                const unsigned off = e < nu ? (unsigned)(rlo * NNZ * 9 + e) * 16u : 0x80000000u;
-                asm volatile("s_mov_b32 m0, %1\n\t"
-                             "s_nop 0\n\t"
-                             "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                             :
-                             : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)(u * 256) * 16u)),
-                               "s"(rs)
-                             : "memory", "m0");
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        (void)nchunk;
-    }
-    if (r >= p.block_rows) return;
-    const SV *urow_s = (const SV *)us + (r - (wgi * 4) / ngroups) * NNZ * 9;
-    const int b = lane >> 4, q = lane & 15;
+    const int nth = PACK ? (int)blockDim.x : 256;
+    const long wgi = xcd_chunk(blockIdx.x, gridDim.x, 2);
     const long n = p.ncols;
-    const long col = (long)cg * 16 + q;
-    const bool ok = col < n;
-    const long colc = ok ? col : n - 1;
+    const int b = lane >> 4, q = lane & 15; // B and C operands: spin b of slot q
+    // the DMA lane (x staged, y through the ring): the piece of slot lane / 4, its spin rotated back
+    const int qd = lane >> 2, bd = ((lane & 3) - (qd >> 1) - (qd >> 3)) & 3;
+    // the lane's output (r, col), if live; xcol: the column its x loads read; the DMA lane's slot
+    // as an output (rowd, cold), if lived; the workgroup's run of color blocks: nu values from row0
+    long r, col, xcol, rowd, cold, row0;
+    bool live, lived;
+    int nu;
+    if constexpr (PACK) {
+        row0 = wgi * a0;
+        const int nrows = (int)min((long)a0, p.block_rows - row0);
+        const int slot = w * 16 + q, rl = slot / (int)n;
+        col = slot - (long)rl * n;
+        live = rl < nrows;
+        r = row0 + (live ? rl : nrows - 1);
+        xcol = col;
+        const int sd = w * 16 + qd, rld = sd / (int)n;
+        cold = sd - (long)rld * n;
+        lived = rld < nrows;
+        rowd = row0 + (lived ? rld : nrows - 1);
+        nu = nrows * NNZ * 9; // <= RW * NNZ * 9: the launcher's LDS for the run
+    } else {
+        const long task = wgi * 4 + w;
+        r = task / a0;
+        const int cg = (int)(task - r * a0);
+        col = (long)cg * 16 + q;
+        live = col < n;
+        xcol = live ? col : n - 1;
+        cold = (long)cg * 16 + qd;
+        lived = cold < n;
+        rowd = r;
+        // a workgroup's 4 tasks span at most 4 rows, consecutive ones
+        row0 = (wgi * 4) / a0;
+        nu = (int)(min((wgi * 4 + 3) / a0, p.block_rows - 1) - row0 + 1) * NNZ * 9; // <= 4 * NNZ * 9
+    }
+    // LDS: the run, the spin matrices (XL), a ring of XL + 1 neighbours x 3 KB per wave (XL)
+    extern __shared__ __attribute__((aligned(16))) char smem_k[];
+    EV *us;
+    E *ks, *ring;
+    unsigned us_a, ring_a; // the LDS addresses of us and ring
+    if constexpr (PACK) {
+        const unsigned xring_w = (unsigned)a1 + (unsigned)w * (NS * 3072u);
+        us = (EV *)smem_k, us_a = lds_u32(smem_k);
+        ring = (E *)(smem_k + xring_w), ring_a = us_a + xring_w;
+        ks = (E *)(smem_k + a1 + (nth >> 6) * NS * 3072);
+    } else {
+        // (the run rounded up to whole DMA passes of 256 lanes: the lanes past it write zeros)
+        __shared__ __attribute__((aligned(16))) EV us_s[(4 * NNZ * 9 + 255) / 256 * 256];
+        __shared__ __attribute__((aligned(16))) E ks_s[XL ? NNZ * 16 : 1];
+        __shared__ __attribute__((aligned(16))) E xr_s[XL ? 4 * NS * 3 * 64 : 1];
+        us = us_s, us_a = lds_u32(us_s), ks = ks_s;
+        ring = xr_s + w * (NS * 192), ring_a = lds_u32(xr_s) + (unsigned)w * (NS * 3072u);
+    }
+    const SV *kron = (const SV *)p.kron;
+    auto stage_spin = [&]() {
+        for (int e = (int)threadIdx.x; e < NNZ * 16; e += nth) ks[e] = kron[e];
+    };
+    if constexpr (!PACK && XL > 0) stage_spin();
+    // the run into LDS: one DMA pass per nth values (launcher: the value array is below 2 GiB), or
+    // -- mixed -- plain loads bounded by the run; read back as broadcasts
+    if constexpr (!same) {
+        const EV *__restrict__ src = (const EV *)p.v + row0 * NNZ * 9;
+        for (int e = (int)threadIdx.x; e < nu; e += nth) us[e] = src[e];
+    } else {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
+        const unsigned base = us_a + (unsigned)w * 1024u;
+        for (int u = 0; u * nth < nu; ++u) {
+            const int e = u * nth + (int)threadIdx.x;
+            const unsigned off = e < nu ? (unsigned)(row0 * NNZ * 9 + e) * 16u : 0x80000000u;
+            dma16(rs, off, base + (unsigned)(u * nth) * 16u);
+        }
+        if constexpr (!PACK) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    if constexpr (!PACK) {
+        __syncthreads();
+        if (r >= p.block_rows) return;
+    }
+    // block columns of the lane's row and of its DMA slot's row: registers (PACK) or scalar loads
+    int jrow_v[PACK ? NNZ : 1], jd_v[PACK && XL > 0 ? NNZ : 1];
+    const ConstPtr<int> jrow_s = (ConstPtr<int>)(p.jj + r * NNZ);
+    auto jcol = [&](int mu) { // block column mu of the lane's row
+        if constexpr (PACK) return jrow_v[mu];
+        else return jrow_s[mu];
+    };
+    auto jdcol = [&](int mu) { // ... of the DMA slot's row
+        if constexpr (PACK) return jd_v[mu];
+        else return jrow_s[mu];
+    };
+    if constexpr (PACK) {
+#pragma unroll
+        for (int mu = 0; mu < NNZ; ++mu) jrow_v[mu] = p.jj[r * NNZ + mu];
+        if constexpr (XL > 0) {
+#pragma unroll
+            for (int mu = 0; mu < NNZ; ++mu) jd_v[mu] = p.jj[rowd * NNZ + mu];
+        }
+    }
     // spin matrices as the A operand: lane 16 k + 4 g + a holds K_mu(a, k)
     const int ka = lane & 3, kk = lane >> 4;
-    const SV *kron = (const SV *)p.kron;
     const int kidx = p.block_im_fast ? ka + kk * 4 : ka * 4 + kk;
-    // block columns and color blocks of the row: wave-uniform
-    const ConstPtr<int> jrow = (ConstPtr<int>)(p.jj + r * NNZ);
     const long xsite = 3 * n * 4; // elements per domain site: (d, n, b)
     auto load_x = [&](int J, E *xv) {
-        const E *xs = x + (long)J * xsite + colc * 4 + b;
+        const E *xs = x + (long)J * xsite + xcol * 4 + b;
 #pragma unroll
         for (int d = 0; d < 3; ++d) xv[d] = xs[d * n * 4];
     };
-    double accR[3] = {0, 0, 0}, accI[3] = {0, 0, 0};
     E xa[3], xb[3];
-    // XL: a ring of XL + 1 neighbours x 3 KB per wave; the DMA lane's piece: column lane / 4 of
-    // the group, its spins rotated as xpos below
-    constexpr int NS = XL + 1;
-    __shared__ __attribute__((aligned(16))) E xr[XL ? 4 * NS * 3 * 64 : 1];
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)x, (short)0, 0x7fffffff, 0x00020000);
-    const int qd = lane >> 2, bd = ((lane & 3) - (qd >> 1) - (qd >> 3)) & 3;
-    const long cold = min((long)cg * 16 + qd, n - 1);
-    const unsigned xoff_d = (unsigned)(cold * 4 + bd) * 16u;
-    const unsigned ring = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)xr + (unsigned)w * (NS * 3072u);
-    auto issue_x = [&](int mu) {
-        const unsigned base = ring + (unsigned)(mu % NS) * 3072u;
-        const unsigned o = (unsigned)((long)jrow[mu] * xsite) * 16u + xoff_d;
+    const unsigned xoff_d = (unsigned)((PACK ? cold : min(cold, n - 1)) * 4 + bd) * 16u;
+    if constexpr (PACK && XL > 0) {
+        stage_spin();
+        // the DMA lanes' block columns: consumed here, so that no load of them is pending
+        // (and waited for by the compiler) inside the loop
 #pragma unroll
-        for (int d = 0; d < 3; ++d)
-            asm volatile("s_mov_b32 m0, %1\n\t"
-                         "s_nop 0\n\t"
-                         "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                         :
-                         : "v"(o + (unsigned)(d * n * 4) * 16u),
-                           "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)d * 1024u)), "s"(rx)
-                         : "memory", "m0");
+        for (int mu = 0; mu < NNZ; ++mu) asm volatile("" : "+v"(jd_v[mu]));
+    }
+    auto issue_x = [&](int mu) {
+        const unsigned base = ring_a + (unsigned)(mu % NS) * 3072u;
+        const unsigned o = (unsigned)((long)jdcol(mu) * xsite) * 16u + xoff_d;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) dma16(rx, o + (unsigned)(d * n * 4) * 16u, base + (unsigned)d * 1024u);
     };
+    // the B lane's position in a ring slot
     const int xpos = 4 * q + ((b + (q >> 1) + (q >> 3)) & 3);
     if constexpr (XL > 0) {
 #pragma unroll
         for (int mu = 0; mu < XL && mu < NNZ; ++mu) issue_x(mu);
     } else {
-        load_x(jrow[0], xa);
+        load_x(jcol(0), xa);
     }
+    if constexpr (PACK) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    const SV *urow_s = (const SV *)us + (r - row0) * NNZ * 9;
+    double accR[3] = {0, 0, 0}, accI[3] = {0, 0, 0};
     // the spin matrix of neighbour mu + 1 is loaded with its x rows; the compiler barrier keeps
     // the unrolled loop from hoisting all 9 spin-matrix loads to the top (36 more VGPRs: fewer
     // waves per SIMD)
@@ -431,11 +461,11 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
             if (mu + XL < NNZ) issue_x(mu + XL);
             // neighbour mu landed: its successors' DMAs (and the next spin load) may stay in flight
             wait_vmcnt(3 * (NNZ - 1 - mu < XL ? NNZ - 1 - mu : XL));
-            const E *xs = xr + w * (NS * 192) + (mu % NS) * 192;
+            const E *xs = ring + (mu % NS) * 192;
 #pragma unroll
             for (int d = 0; d < 3; ++d) xa[d] = xs[d * 64 + xpos];
         } else if (mu + 1 < NNZ) {
-            load_x(jrow[mu + 1], xb);
+            load_x(jcol(mu + 1), xb);
             if constexpr (kpf) Kn = kron[(mu + 1) * 16 + kidx];
         }
         const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : E(kron[mu * 16 + kidx]);
@@ -466,229 +496,18 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_kernel(const KronArgs p, in
     }
     if constexpr (XL > 0) {
         if (p.ylds) {
-            // C lane 16 a + q -> ring position xpos (a in place of b); lane l stores column l / 4
-            E *ys = xr + w * (NS * 192);
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                ys[i * 64 + xpos] = Ops<E>::scale(E{accR[i], accI[i]}, p.alpha_re, p.alpha_im);
-            asm volatile("" ::: "memory");
-            const long cs = (long)cg * 16 + qd;
-            if (cs >= n) return;
-            const int ad = bd;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                E *yp = y + ((r * 3 + i) * n + cs) * 4 + ad;
-                E o = ys[i * 64 + lane];
-                if (p.add) o = Ops<E>::add(o, *yp);
-                *yp = o;
-            }
-            return;
-        }
-    }
-    if (!ok) return;
-    // C lane 16 a + q: spin a of column q
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        E *yp = y + ((r * 3 + i) * n + col) * 4 + b;
-        E o = Ops<E>::scale(E{accR[i], accI[i]}, p.alpha_re, p.alpha_im);
-        if (p.add) o = Ops<E>::add(o, *yp);
-        *yp = o;
-    }
-}
-
-// The same kernel for rhs counts below 16 that divide 16 W (W <= 4 waves): a wave's 16 column
-// slots are (row, column) pairs of the workgroup's RW = 16 W / n consecutive block rows, so no lane
-// idles (at n = 12 one wave per row left 4 of 16 slots empty: 25 % of the VALU and MFMA work).
-// The row's block columns and color blocks become per-lane (LDS reads of the staged color blocks,
-// block columns loaded per lane); the spin matrices stay the MFMA's A operand.
-// XL: the neighbours' x pieces staged by LDS-DMA instead of VGPR loads.  The MFMA's B operand
-// wants lane 16 b + q = spin b of slot q, but spin is the fastest index of x in memory, so a
-// 16-lane quarter of such a load touches 16 pieces 64 B apart (8 cache lines; 32 TA/TCP accesses
-// per 1-KB instruction against 8 for a linear one, and TA/TD busy 85-92 %).  The DMA instead
-// moves each slot's 4 spins as one 64-B piece (lane l: slot l / 4), writes them lane-linear into
-// the wave's ring (XL neighbours ahead, 3 KB per neighbour: deeper prefetch costs LDS, not
-// VGPRs), and the B lanes read them back with the spins rotated (position 4 q + (b + q / 2 +
-// q / 8) mod 4: the 16-B granules of any 8 or 16 lanes reading together fall on distinct banks).
-// EV = float2 (bsr.kron_mixed): as in bsr_kron_mfma_kernel -- the colour run in LDS as stored,
-// staged by plain 8-byte loads bounded by the run and LDS writes (rw is even here, so the run's
-// start is a multiple of 16 from the base, but the base itself is only 8-byte aligned), widened
-// at the LDS read; the ks image widened where it is filled.
-template <int NNZ, bool kpf = false, int XL = 0, typename EV = double2>
-__global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArgs p, int rw, int xring) {
-    constexpr int NS = XL + 1;
-    typedef double2 E;
-    constexpr bool same = std::is_same<EV, E>::value;
-    typedef typename BsrStored<EV, E>::type SV; // a value as stored: reading it as E widens
-    const E *__restrict__ x = (const E *)p.x;
-    E *__restrict__ y = (E *)p.y;
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x, nwg = gridDim.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int cnt = xcd < r8 ? q8 + 1 : q8, qx = bid >> 3, npart = cnt / 2;
-    const int loc = (npart > 0 && qx < npart * 2) ? (qx % 2) * npart + qx / 2 : qx;
-    const long wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + loc;
-    const long r0 = wgi * rw;
-    const int nrows = (int)min((long)rw, p.block_rows - r0);
-    const long n = p.ncols;
-    const int b = lane >> 4, q = lane & 15;
-    const int slot = w * 16 + q, rl = slot / (int)n;
-    const long col = slot - (long)rl * n;
-    const bool live = rl < nrows;
-    const int rlc = live ? rl : nrows - 1;
-    const long r = r0 + rlc;
-    // the color blocks of the workgroup's rows (one contiguous run) into LDS by one DMA pass
-    // (dynamic LDS: rw rows of NNZ 3x3 blocks)
-    extern __shared__ __attribute__((aligned(16))) char smem_k[];
-    EV *us = (EV *)smem_k;
-    if constexpr (!same) {
-        const int nu = nrows * NNZ * 9; // <= rw * NNZ * 9: the launcher's LDS for the run
-        const EV *__restrict__ src = (const EV *)p.v + r0 * NNZ * 9;
-        for (int e = (int)threadIdx.x; e < nu; e += (int)blockDim.x) us[e] = src[e];
-    } else {
-        const int nu = nrows * NNZ * 9;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)p.v, (short)0, (int)(p.block_rows * NNZ * 9 * 16), 0x00020000);
-        const unsigned base = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)smem_k +
-                              (unsigned)w * 1024u;
-        const int nth = (int)blockDim.x;
-        for (int u = 0; u * nth < nu; ++u) {
-            const int e = u * nth + (int)threadIdx.x;
-            const unsigned off = e < nu ? (unsigned)(r0 * NNZ * 9 + e) * 16u : 0x80000000u;
-            asm volatile("s_mov_b32 m0, %1\n\t"
-                         "s_nop 0\n\t"
-                         "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                         :
-                         : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)(u * nth) * 16u)),
-                           "s"(rs)
-                         : "memory", "m0");
-        }
-    }
-    // the lane's row: block columns (per lane), then the first neighbour's x
-    int jrow[NNZ];
-#pragma unroll
-    for (int mu = 0; mu < NNZ; ++mu) jrow[mu] = p.jj[r * NNZ + mu];
-    const int ka = lane & 3, kk = lane >> 4;
-    const SV *kron = (const SV *)p.kron;
-    const int kidx = p.block_im_fast ? ka + kk * 4 : ka * 4 + kk;
-    const long xsite = 3 * n * 4;
-    auto load_x = [&](int J, E *xv) {
-        const E *xs = x + (long)J * xsite + col * 4 + b;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) xv[d] = xs[d * n * 4];
-    };
-    E xa[3], xb[3];
-    // XL: the DMA lane's piece (slot lane / 4, spin rotated back) and its slot's block columns
-    int jd[XL > 0 ? NNZ : 1];
-    unsigned xoff_d = 0, xring_w = 0;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)x, (short)0, 0x7fffffff, 0x00020000);
-    if constexpr (XL > 0) {
-        const int qd = lane >> 2, bd = ((lane & 3) - (qd >> 1) - (qd >> 3)) & 3;
-        const int sd = w * 16 + qd, rld = sd / (int)n;
-        const long cold = sd - (long)rld * n;
-        const long rd = r0 + (rld < nrows ? rld : nrows - 1);
-#pragma unroll
-        for (int mu = 0; mu < NNZ; ++mu) jd[mu] = p.jj[rd * NNZ + mu];
-        xoff_d = (unsigned)(cold * 4 + bd) * 16u;
-        xring_w = (unsigned)xring + (unsigned)w * (NS * 3072u);
-    }
-    const unsigned lds0 = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)smem_k;
-    // XL: the spin matrices in LDS after the rings -- no vector-memory load in the main loop,
-    // where the compiler's own vmcnt waits (blind to the DMAs) would drain the x ring
-    E *ks = (E *)(smem_k + xring + (int)(blockDim.x >> 6) * NS * 3072);
-    if constexpr (XL > 0) {
-        for (int e = (int)threadIdx.x; e < NNZ * 16; e += (int)blockDim.x) ks[e] = kron[e];
-        // the DMA lanes' block columns: consumed here, so that no load of them is pending
-        // (and waited for by the compiler) inside the loop
-#pragma unroll
-        for (int mu = 0; mu < NNZ; ++mu) asm volatile("" : "+v"(jd[mu]));
-    }
-    auto issue_x = [&](int mu) {
-        const unsigned base = lds0 + xring_w + (unsigned)(mu % NS) * 3072u;
-        const unsigned o = (unsigned)((long)jd[mu] * xsite) * 16u + xoff_d;
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            asm volatile("s_mov_b32 m0, %1\n\t"
-                         "s_nop 0\n\t"
-                         "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                         :
-                         : "v"(o + (unsigned)(d * n * 4) * 16u),
-                           "s"(__builtin_amdgcn_readfirstlane(base + (unsigned)d * 1024u)), "s"(rx)
-                         : "memory", "m0");
-    };
-    // the B lane's position in a ring slot
-    const int xpos = 4 * q + ((b + (q >> 1) + (q >> 3)) & 3);
-    if constexpr (XL > 0) {
-#pragma unroll
-        for (int mu = 0; mu < XL && mu < NNZ; ++mu) issue_x(mu);
-    } else {
-        load_x(jrow[0], xa);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const SV *urow_s = (const SV *)us + rlc * NNZ * 9;
-    double accR[3] = {0, 0, 0}, accI[3] = {0, 0, 0};
-    // the spin matrix of neighbour mu + 1 is loaded with its x rows; the compiler barrier keeps
-    // the unrolled loop from hoisting all 9 spin-matrix loads to the top (36 more VGPRs: fewer
-    // waves per SIMD)
-    E Kc = XL > 0 ? E{} : E(kron[kidx]);
-#pragma unroll
-    for (int mu = 0; mu < NNZ; ++mu) {
-        if constexpr (kpf) asm volatile("" ::: "memory");
-        E Kn = Kc;
-        if constexpr (XL > 0) {
-            // the ring slot of neighbour mu + XL was read in iteration mu - 1: those reads are done
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (mu + XL < NNZ) issue_x(mu + XL);
-            // neighbour mu landed: its successors' DMAs (and the next spin load) may stay in flight
-            wait_vmcnt(3 * (NNZ - 1 - mu < XL ? NNZ - 1 - mu : XL));
-            const E *xs = (const E *)(smem_k + xring_w + (mu % NS) * 3072);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) xa[d] = xs[d * 64 + xpos];
-        } else if (mu + 1 < NNZ) {
-            load_x(jrow[mu + 1], xb);
-            if constexpr (kpf) Kn = kron[(mu + 1) * 16 + kidx];
-        }
-        const E K = XL > 0 ? ks[mu * 16 + kidx] : kpf ? Kc : E(kron[mu * 16 + kidx]);
-        Kc = Kn;
-        E t[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            t[i] = Ops<E>::zero();
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const long ui = mu * 9 + (p.block_im_fast ? i + d * 3 : i * 3 + d);
-                t[i] = Ops<E>::fma(urow_s[ui], xa[d], t[i]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            accR[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(K.x, t[i].x, accR[i], 0, 0, 0);
-            accR[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(-K.y, t[i].y, accR[i], 0, 0, 0);
-            accI[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(K.x, t[i].y, accI[i], 0, 0, 0);
-            accI[i] = __builtin_amdgcn_mfma_f64_4x4x4f64(K.y, t[i].x, accI[i], 0, 0, 0);
-        }
-        if (XL == 0 && mu + 1 < NNZ) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d) xa[d] = xb[d];
-        }
-    }
-    if constexpr (XL > 0) {
-        if (p.ylds) {
             // C lane 16 a + q -> ring position xpos (the B read's map, a in place of b); then
             // lane l stores the piece of slot l / 4: each slot's 4 spins one 64-B run
-            E *ys = (E *)(smem_k + xring_w);
+            E *ys = ring;
 #pragma unroll
             for (int i = 0; i < 3; ++i)
                 ys[i * 64 + xpos] = Ops<E>::scale(E{accR[i], accI[i]}, p.alpha_re, p.alpha_im);
             asm volatile("" ::: "memory");
-            const int qd = lane >> 2, ad = ((lane & 3) - (qd >> 1) - (qd >> 3)) & 3;
-            const int sd = w * 16 + qd, rld = sd / (int)n;
-            if (rld >= nrows) return;
-            const long cold = sd - (long)rld * n;
+            if (!lived) return;
+            const long rs = PACK ? row0 + (w * 16 + qd) / (int)n : r;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                E *yp = y + (((r0 + rld) * 3 + i) * n + cold) * 4 + ad;
+                E *yp = y + ((rs * 3 + i) * n + cold) * 4 + bd;
                 E o = ys[i * 64 + lane];
                 if (p.add) o = Ops<E>::add(o, *yp);
                 *yp = o;
@@ -707,6 +526,11 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
     }
 }
 
+/// The two forms by the names the launcher, the tests and the documents know them by
+template <int NNZ, bool kpf, int XL, typename EV>
+constexpr auto *bsr_kron_mfma_kernel = &bsr_kron_mfma_form_kernel<false, NNZ, kpf, XL, EV>;
+template <int NNZ, bool kpf, int XL, typename EV>
+constexpr auto *bsr_kron_mfma_packed_kernel = &bsr_kron_mfma_form_kernel<true, NNZ, kpf, XL, EV>;
 
 // complex<double>, 3x3 color blocks, 4x4 spin matrices with at most two nonzeros per row (the
 // Wilson projectors 1 -+ gamma_mu, the identity, gamma matrices), from 8 rhs columns, spin first
@@ -727,22 +551,37 @@ __global__ void __launch_bounds__(256) bsr_kron_mfma_packed_kernel(const KronArg
 // compact lattice box).
 constexpr int KS_WAVE_LDS = 2 * 4096 + 2 * 512 + 2 * 256;
 
-/// DMA of 16 (or 4: dword) bytes per lane into LDS at m0 = base (+ 16 or 4 per lane)
-__device__ __forceinline__ void dma16(unsigned off, unsigned base, __amdgpu_buffer_rsrc_t r) {
-    asm volatile("s_mov_b32 m0, %1\n\t"
-                 "s_nop 0\n\t"
-                 "buffer_load_dwordx4 %0, %2, 0 offen lds"
-                 :
-                 : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base)), "s"(r)
-                 : "memory", "m0");
-}
-__device__ __forceinline__ void dma4(unsigned off, unsigned base, __amdgpu_buffer_rsrc_t r) {
-    asm volatile("s_mov_b32 m0, %1\n\t"
-                 "s_nop 0\n\t"
-                 "buffer_load_dword %0, %2, 0 offen lds"
-                 :
-                 : "v"(off), "s"(__builtin_amdgcn_readfirstlane(base)), "s"(r)
-                 : "memory", "m0");
+/// The lane's pair in the spin-first kernels: wave w of XCD-contiguous workgroup wgi takes pairs
+/// 64 (4 wgi + w) ... of the block_rows * n (row slot, column) pairs (launcher: below 2^31)
+struct KronPair {
+    int n, total;  ///< rhs columns, pairs
+    int pw0;       ///< the wave's first pair
+    int slot, col; ///< the lane's pair (past the end: the last one)
+    bool live;     ///< ... and whether it has one
+    /// false: the wave has no pair at all
+    __device__ __forceinline__ bool init(const KronArgs &p, int lane, int w) {
+        n = (int)p.ncols;
+        total = (int)(p.block_rows * n);
+        pw0 = (xcd_chunk(blockIdx.x, gridDim.x) * 4 + w) * 64;
+        if (pw0 >= total) return false;
+        const int pp = min(pw0 + lane, total - 1);
+        live = pw0 + lane < total;
+        slot = pp / n, col = pp - slot * n;
+        return true;
+    }
+};
+
+/// The accumulators of a step pinned: its products finish before what follows is issued (MEM:
+/// and no memory access moves across)
+template <bool MEM> __device__ __forceinline__ void pin_products(double (&ar)[3][4], double (&ai)[3][4]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if constexpr (MEM)
+            asm volatile("" : "+v"(ar[i][0]), "+v"(ar[i][1]), "+v"(ar[i][2]), "+v"(ar[i][3]),
+                         "+v"(ai[i][0]), "+v"(ai[i][1]), "+v"(ai[i][2]), "+v"(ai[i][3])::"memory");
+        else
+            asm volatile("" : "+v"(ar[i][0]), "+v"(ar[i][1]), "+v"(ar[i][2]), "+v"(ar[i][3]),
+                         "+v"(ai[i][0]), "+v"(ai[i][1]), "+v"(ai[i][2]), "+v"(ai[i][3]));
 }
 
 __global__ void __launch_bounds__(256) bsr_kron_spin_kernel(const KronArgs p) {
@@ -750,27 +589,20 @@ __global__ void __launch_bounds__(256) bsr_kron_spin_kernel(const KronArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_s[];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // XCD-contiguous workgroup order: the hardware deals workgroups round robin over the 8 XCDs
-    const int bid = blockIdx.x, nwg = gridDim.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     // (launcher: pairs, x, values and block columns below 2^31 elements / bytes)
-    const int n = (int)p.ncols, nnz = p.nnz;
-    const int total = (int)(p.block_rows * n);
-    const int pw0 = (wgi * 4 + w) * 64; // the wave's first pair
-    if (pw0 >= total) return;
+    KronPair pr;
+    if (!pr.init(p, lane, w)) return;
+    const int n = pr.n, nnz = p.nnz, total = pr.total, pw0 = pr.pw0;
+    const int slot = pr.slot, col = pr.col;
+    const bool live = pr.live;
     const int slot_lo = pw0 / n;
     const int rows_w = min(pw0 + 63, total - 1) / n - slot_lo + 1; // <= 9 (n >= 8)
     const int *perm = p.perm;
     auto row_of = [&](int slot) -> int { return perm ? perm[slot] : slot; };
-    // the lane's pair
-    const int pp = min(pw0 + lane, total - 1);
-    const bool live = pw0 + lane < total;
-    const int slot = pp / n, col = pp - slot * n;
     const int wr = slot - slot_lo;
     // LDS per wave: x slots [2][4096], U slots [2][512], J slots [2][256]
     char *wl = smem_s + w * KS_WAVE_LDS;
-    const unsigned wl_a = (unsigned)(size_t)(const __attribute__((address_space(3))) void *)wl;
+    const unsigned wl_a = lds_u32(wl);
     const E *xs = (const E *)wl;
     const E *us = (const E *)(wl + 8192);
     const int *js = (const int *)(wl + 9216);
@@ -817,11 +649,11 @@ __global__ void __launch_bounds__(256) bsr_kron_spin_kernel(const KronArgs p) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const unsigned off = (unsigned)((jx[k] * 3 + d) * xd + xcolb[k]) * 16u;
-            dma16((xbad >> k & 1) ? 0x80000000u : off, xb + (unsigned)k * 1024u, rx);
+            dma16(rx, (xbad >> k & 1) ? 0x80000000u : off, xb + (unsigned)k * 1024u);
         }
-        if (lane < 32) dma16((unsigned)(ubase + mu * 9 + d * ustep) * 16u | ubad, wl_a + 8192u + (unsigned)par * 512u, ru);
+        if (lane < 32) dma16(ru, (unsigned)(ubase + mu * 9 + d * ustep) * 16u | ubad, wl_a + 8192u + (unsigned)par * 512u);
         if (d == 0 && mu + 1 < nnz)
-            dma4((unsigned)(jbase + mu + 1) * 4u | jbad, wl_a + 9216u + (unsigned)((mu + 1) & 1) * 256u, rj);
+            dma4(rj, (unsigned)(jbase + mu + 1) * 4u | jbad, wl_a + 9216u + (unsigned)((mu + 1) & 1) * 256u);
     };
     double ar[3][4], ai[3][4];
 #pragma unroll
@@ -893,22 +725,12 @@ __global__ void __launch_bounds__(256) bsr_kron_spin_kernel(const KronArgs p) {
             }
             // the step's products finish before the next step's waits and DMAs (otherwise the
             // compiler overlaps the steps and holds two steps' x values: 167 VGPRs)
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                asm volatile("" : "+v"(ar[i][0]), "+v"(ar[i][1]), "+v"(ar[i][2]), "+v"(ar[i][3]),
-                             "+v"(ai[i][0]), "+v"(ai[i][1]), "+v"(ai[i][2]), "+v"(ai[i][3]));
+            pin_products<false>(ar, ai);
         }
     }
     if (!live) return;
-    E *yp = (E *)p.y + ((long)orow * 3 * n + col) * 4;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            E o = Ops<E>::scale(E{ar[i][a], ai[i][a]}, p.alpha_re, p.alpha_im);
-            if (p.add) o = Ops<E>::add(o, yp[(long)i * n * 4 + a]);
-            yp[(long)i * n * 4 + a] = o;
-        }
+    store_outputs<E, 3, 4>((E *)p.y + ((long)orow * 3 * n + col) * 4, n, p.alpha_re, p.alpha_im, p.add,
+                           [&](int i, int a) { return E{ar[i][a], ai[i][a]}; });
 }
 
 
@@ -947,17 +769,11 @@ __global__ void __launch_bounds__(256) bsr_kron_xor_kernel(const KronArgs p) {
     typedef double2 E;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = blockIdx.x, nwg = gridDim.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int wgi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     // (launcher: pairs, x and values below 2^31 elements)
-    const int n = (int)p.ncols, nnz = p.nnz;
-    const int total = (int)(p.block_rows * n);
-    const int pw0 = (wgi * 4 + w) * 64;
-    if (pw0 >= total) return;
-    const int pp = min(pw0 + lane, total - 1);
-    const bool live = pw0 + lane < total;
-    const int slot = pp / n, col = pp - slot * n;
+    KronPair pr;
+    if (!pr.init(p, lane, w)) return;
+    const int n = pr.n, nnz = p.nnz, slot = pr.slot, col = pr.col;
+    const bool live = pr.live;
     const int row = p.perm ? p.perm[slot] : slot;
     const E *x = (const E *)p.x, *v = (const E *)p.v;
     const int *jrow = p.jj + (long)row * nnz;
@@ -1012,10 +828,7 @@ __global__ void __launch_bounds__(256) bsr_kron_xor_kernel(const KronArgs p) {
                     ai[i][a] = __builtin_fma(uv[i].y, hr[a], ai[i][a]);
                 }
             // the step's products finish before the next step's loads are issued
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                asm volatile("" : "+v"(ar[i][0]), "+v"(ar[i][1]), "+v"(ar[i][2]), "+v"(ar[i][3]),
-                             "+v"(ai[i][0]), "+v"(ai[i][1]), "+v"(ai[i][2]), "+v"(ai[i][3])::"memory");
+            pin_products<true>(ar, ai);
 #pragma unroll
             for (int b = 0; b < 4; ++b) xv[b] = xn[b];
 #pragma unroll
@@ -1024,15 +837,8 @@ __global__ void __launch_bounds__(256) bsr_kron_xor_kernel(const KronArgs p) {
         J = Jn;
     }
     if (!live) return;
-    E *yp = (E *)p.y + ((long)row * 3 * n + col) * 4;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            E o = Ops<E>::scale(E{ar[i][a], ai[i][a]}, p.alpha_re, p.alpha_im);
-            if (p.add) o = Ops<E>::add(o, yp[(long)i * n * 4 + a]);
-            yp[(long)i * n * 4 + a] = o;
-        }
+    store_outputs<E, 3, 4>((E *)p.y + ((long)row * 3 * n + col) * 4, n, p.alpha_re, p.alpha_im, p.add,
+                           [&](int i, int a) { return E{ar[i][a], ai[i][a]}; });
 }
 
 // The adjoint, x with the image labels of A (the reference's local Kronecker operators throw
@@ -1190,15 +996,8 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_kernel(const KronAdjArgs p, 
         }
     }
     if (!live) return;
-    E *ys = y + (r * BD * p.ncols + c) * KD;
-#pragma unroll
-    for (int d = 0; d < BD; ++d)
-#pragma unroll
-        for (int b = 0; b < KD; ++b) {
-            E o = Ops<E>::scale(acc[d][b], p.alpha_re, p.alpha_im);
-            if (p.add) o = Ops<E>::add(o, ys[d * p.ncols * KD + b]);
-            ys[d * p.ncols * KD + b] = o;
-        }
+    store_outputs<E, BD, KD>(y + (r * BD * p.ncols + c) * KD, p.ncols, p.alpha_re, p.alpha_im, p.add,
+                             [&](int d, int b) { return acc[d][b]; });
 }
 
 /// Any block / Kronecker sizes: one thread per output element (site, d, column, b)
@@ -1242,10 +1041,35 @@ __global__ void __launch_bounds__(256) bsr_kron_adj_generic_kernel(const KronAdj
 
 constexpr long KRON_LDS_BYTES = 64 * 1024;
 
+/// 3x3 color blocks and 4x4 spin matrices: the sizes of the specialised kernels
+template <typename Args> bool is_3x3_4x4(const Args &a) { return a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4; }
+
+/// The matrix-core kernels' XL: neighbours of x staged ahead by LDS-DMA ("bsr.kron_xlds", 0-3); 0
+/// where x or y reach beyond the DMA's 32-bit buffer offsets
+int kron_xl(const KronArgs &a) {
+    const bool fits = std::max(a.block_rows * 12L, a.x_rows * 4L) * a.ncols * 16 < (1L << 31);
+    return fits ? std::max(0, std::min(3, g_bsr_tune.kron_xlds)) : 0;
+}
+
+/// f(EV{}, E{}) with EV the values' type and E the vectors': the same type, or single-precision
+/// values under double vectors
+template <typename F> void with_kron_types(const BsrDesc &d, F f) {
+    if (d.tv == d.t) switch (d.t) {
+        case SBX_CDOUBLE: return f(double2{}, double2{});
+        case SBX_CFLOAT: return f(float2{}, float2{});
+        case SBX_DOUBLE: return f(double{}, double{});
+        case SBX_FLOAT: return f(float{}, float{});
+        default: break;
+        }
+    if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return f(float2{}, double2{});
+    if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return f(float{}, double{});
+    throw Error("kron bsr: unsupported type");
+}
+
 /// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
 template <typename EV, typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
-    if (g_bsr_tune.kron_adj && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4) {
+    if (g_bsr_tune.kron_adj && is_3x3_4x4(a)) {
         const int cpg = (int)std::min<long>(a.ncols, 256);
         const bool stage = a.ncols >= KRON_ADJ_STAGE_COLS && g_bsr_tune.kron_adj != 2;
         const int S = std::min(256 / cpg, stage ? KRON_ADJ_SITES : 256);
@@ -1255,12 +1079,11 @@ template <typename EV, typename E> void launch_kron_adj_typed(const KronAdjArgs 
         const long lds = (long)((stage ? KRON_ADJ_CHUNK * 9 : 0) + (long)a.nnz * 16) * (long)sizeof(E);
         if (lds <= KRON_LDS_BYTES && gx < (1L << 31) && gy < 65536) {
             g_bsr_tune.last = 15;
-            if (stage)
-                hipLaunchKernelGGL((bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, true>), dim3((unsigned)gx, (unsigned)gy),
-                                   dim3(nth), (size_t)lds, s, a, S, cpg);
-            else
-                hipLaunchKernelGGL((bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, false>), dim3((unsigned)gx, (unsigned)gy),
-                                   dim3(nth), (size_t)lds, s, a, S, cpg);
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(nth), (size_t)lds, s, a, S, cpg);
+            };
+            if (stage) go(bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, true>);
+            else go(bsr_kron_adj_kernel<EV, E, 3, 3, 4, 4, false>);
             SBX_HIP_CHECK(hipGetLastError());
             return;
         }
@@ -1298,17 +1121,7 @@ void launch_bsr_kron_adj(const BsrDesc &d, int device) {
     a.alpha_im = d.alpha.im;
     a.add = d.add ? 1 : 0;
     hipStream_t s = get_stream(device);
-    // (values' type, vectors' type): the same type, or single-precision values under double vectors
-    if (d.tv == d.t) switch (d.t) {
-        case SBX_CDOUBLE: return launch_kron_adj_typed<double2, double2>(a, s);
-        case SBX_CFLOAT: return launch_kron_adj_typed<float2, float2>(a, s);
-        case SBX_DOUBLE: return launch_kron_adj_typed<double, double>(a, s);
-        case SBX_FLOAT: return launch_kron_adj_typed<float, float>(a, s);
-        default: break;
-        }
-    if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_kron_adj_typed<float2, double2>(a, s);
-    if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_kron_adj_typed<float, double>(a, s);
-    throw Error("kron bsr: unsupported type");
+    with_kron_types(d, [&](auto ev, auto e) { launch_kron_adj_typed<decltype(ev), decltype(e)>(a, s); });
 }
 
 /// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
@@ -1319,8 +1132,8 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
     const long row_bytes = (long)a.nnz * (a.bi * a.bd * sizeof(EV) + sizeof(int));
     // the spin-first kernels read their tables of doubles: same-type products only
     if constexpr (std::is_same<E, double2>::value && same) {
-        if (g_bsr_tune.kron_spin == 2 && a.xtab && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 &&
-            a.nnz >= 1 && a.ncols >= g_bsr_tune.kron_spin_min_cols && a.x_rows * 4 * a.ncols < (1L << 31) &&
+        if (g_bsr_tune.kron_spin == 2 && a.xtab && is_3x3_4x4(a) && a.nnz >= 1 &&
+            a.ncols >= g_bsr_tune.kron_spin_min_cols && a.x_rows * 4 * a.ncols < (1L << 31) &&
             a.block_rows * a.ncols + 1024 < (1L << 31)) {
             const long waves = (a.block_rows * a.ncols + 63) / 64, blocks = (waves + 3) / 4;
             if (blocks < (1L << 31)) {
@@ -1332,8 +1145,8 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
                 return;
             }
         }
-        if (g_bsr_tune.kron_spin == 1 && a.ktab && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 && a.nnz >= 1 &&
-            a.nnz <= 64 && a.ncols >= std::max(8L, g_bsr_tune.kron_spin_min_cols) &&
+        if (g_bsr_tune.kron_spin == 1 && a.ktab && is_3x3_4x4(a) && a.nnz >= 1 && a.nnz <= 64 &&
+            a.ncols >= std::max(8L, g_bsr_tune.kron_spin_min_cols) &&
             a.block_rows * a.nnz * 9 * 16 < (1L << 31) && a.x_rows * 4 * a.ncols * 16 < (1L << 31) &&
             a.block_rows * a.ncols + 1024 < (1L << 31)) {
             const long waves = (a.block_rows * a.ncols + 63) / 64, blocks = (waves + 3) / 4;
@@ -1358,7 +1171,7 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
         // measured.
         // (the 2 GiB bound: the colour run's LDS-DMA buffer offsets; the mixed form stages the run
         // by plain loads with 64-bit addresses)
-        if (g_bsr_tune.kron_mfma && a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 && a.nnz == 9 &&
+        if (g_bsr_tune.kron_mfma && is_3x3_4x4(a) && a.nnz == 9 &&
             a.ncols >= g_bsr_tune.kron_mfma_min_cols && (!same || a.block_rows * 81L * 16 < (1L << 31))) {
             // packed slots: W waves of 16 (row, column) slots hold RW = 16 W / n whole rows
             int wpk = 0;
@@ -1382,8 +1195,7 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
                     if (same) check_dma_lds("bsr_kron_mfma_packed_kernel", lds_cb, (rw * 81L + nth - 1) / nth, nth);
                     // x by LDS-DMA: a ring of 2 x 3 KB per wave after the color blocks (lds_cb is
                     // a multiple of 16); 32-bit buffer offsets
-                    const int xl = std::max(a.block_rows * 12L, a.x_rows * 4L) * a.ncols * 16 < (1L << 31)
-                                       ? std::max(0, std::min(3, g_bsr_tune.kron_xlds)) : 0;
+                    const int xl = kron_xl(a);
                     // (+ the 9 spin matrices)
                     const size_t lds_bytes = lds_cb + (xl > 0 ? (size_t)wpk * (xl + 1) * 3072 + 9 * 16 * 16 : 0);
                     if (xl) check_dma_lds("bsr_kron_mfma_packed_kernel x ring", lds_bytes, 0, 0, (long)lds_cb + wpk * (xl + 1) * 3072L + 9 * 16 * 16);
@@ -1396,9 +1208,7 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
                     if (xl == 1) go(bsr_kron_mfma_packed_kernel<9, true, 1, EV>);
                     else if (xl == 2) go(bsr_kron_mfma_packed_kernel<9, true, 2, EV>);
                     else if (xl == 3) go(bsr_kron_mfma_packed_kernel<9, true, 3, EV>);
-                    else
-                        hipLaunchKernelGGL((bsr_kron_mfma_packed_kernel<9, true, 0, EV>), dim3((unsigned)blocks),
-                                           dim3(64 * wpk), lds_bytes, s, a, rw, (int)lds_cb);
+                    else go(bsr_kron_mfma_packed_kernel<9, true, 0, EV>);
                     SBX_HIP_CHECK(hipGetLastError());
                     return;
                 }
@@ -1408,30 +1218,27 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
             if (blocks < (1L << 31)) {
                 g_bsr_tune.last = 5;
                 // x by LDS-DMA (32-bit buffer offsets)
-                const int xl = std::max(a.block_rows * 12L, a.x_rows * 4L) * a.ncols * 16 < (1L << 31)
-                                   ? std::max(0, std::min(3, g_bsr_tune.kron_xlds)) : 0;
+                const int xl = kron_xl(a);
                 auto go = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)ngroups);
+                    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, a, (int)ngroups, 0);
                 };
                 if (xl == 1) go(bsr_kron_mfma_kernel<9, false, 1, EV>);
                 else if (xl == 2) go(bsr_kron_mfma_kernel<9, false, 2, EV>);
                 else if (xl == 3) go(bsr_kron_mfma_kernel<9, false, 3, EV>);
-                else
-                    hipLaunchKernelGGL((bsr_kron_mfma_kernel<9, false, 0, EV>), dim3((unsigned)blocks), dim3(256), 0,
-                                       s, a, (int)ngroups);
+                else go(bsr_kron_mfma_kernel<9, false, 0, EV>);
                 SBX_HIP_CHECK(hipGetLastError());
                 return;
             }
         }
     }
-    if (a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4 && a.nnz == 9 && a.ncols >= 4 &&
+    if (is_3x3_4x4(a) && a.nnz == 9 && a.ncols >= 4 &&
         row_bytes * (256 / std::min<long>(a.ncols, 256)) <= KRON_LDS_BYTES) {
         const int cpg = (int)std::min<long>(a.ncols, 256);
         const int S = 256 / cpg;
         const dim3 grid((unsigned)((a.block_rows + S - 1) / S), (unsigned)((a.ncols + cpg - 1) / cpg));
         hipLaunchKernelGGL((bsr_kron_lds_kernel<EV, E, 3, 3, 4, 4, 9>), grid, dim3(256),
                            (size_t)(row_bytes * S), s, a, S, cpg);
-    } else if (a.bi == 3 && a.bd == 3 && a.ki == 4 && a.kd == 4) {
+    } else if (is_3x3_4x4(a)) {
         const long total = a.block_rows * a.ncols;
         const long blocks = std::min((total + 255) / 256, 65536L);
         hipLaunchKernelGGL((bsr_kron_kernel<EV, E, 3, 3, 4, 4>), dim3(blocks), dim3(256), 0, s, a);
@@ -1478,17 +1285,7 @@ void launch_bsr_kron(const BsrDesc &d, int device) {
     // (the spin-first tables: null on a mixed launch, whose operator never builds them)
     a.ktab = d.tv == d.t ? d.kron_terms : nullptr;
     a.xtab = d.tv == d.t ? d.kron_xor : nullptr;
-    // (values' type, vectors' type): the same type, or single-precision values under double vectors
-    if (d.tv == d.t) switch (d.t) {
-        case SBX_CDOUBLE: return launch_kron_typed<double2, double2>(a, s);
-        case SBX_CFLOAT: return launch_kron_typed<float2, float2>(a, s);
-        case SBX_DOUBLE: return launch_kron_typed<double, double>(a, s);
-        case SBX_FLOAT: return launch_kron_typed<float, float>(a, s);
-        default: break;
-        }
-    if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return launch_kron_typed<float2, double2>(a, s);
-    if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return launch_kron_typed<float, double>(a, s);
-    throw Error("kron bsr: unsupported type");
+    with_kron_types(d, [&](auto ev, auto e) { launch_kron_typed<decltype(ev), decltype(e)>(a, s); });
 }
 
 } // namespace sbx

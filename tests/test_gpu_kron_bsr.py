@@ -226,6 +226,61 @@ def test_kron_mfma_kernel(gpu, ncols, L, bif, sparse):
         assert np.array_equal(out, ref), form
 
 
+@pytest.mark.parametrize("ncols", [1, 2, 3, 4, 5, 6, 7])
+def test_kron_mfma_low_columns(gpu, ncols):
+    """The matrix-core kernels below 8 columns ("bsr.kron_mfma_min_cols" 1), 3^4 sites: the packed
+    kernel with 2, 4, 3, 4 and 3 waves and 32, 32, 16, 16 and 8 rows per workgroup at 1, 2, 3, 4
+    and 6 columns (81 = 2 * 32 + 17 = 5 * 16 + 1 = 10 * 8 + 1: a short last workgroup in each),
+    the one-row-per-wave kernel at 5 and 7 columns (they do not divide 16 W) and with packing off
+    (a last workgroup with one live wave); x staged or loaded per lane, y per lane or through the
+    ring; complex alpha, beta, powers; integer data, exact."""
+    import torch
+    import superbblas_amd as sb
+    L, spin, color, power = 3, 4, 3, 2
+    ii, jj, vals, kron = kron_lattice(L, spin, color)
+    V = L ** 4
+    n = V * color * ncols * spin
+    g = np.arange(n)
+    x = ((g % 5 - 2) + 1j * (g % 3 - 1)).astype(np.complex128)
+    y0 = ((np.arange(n * power) % 7 - 3) + 1j).astype(np.complex128)
+    alpha, beta = 1 - 1j, 2.0
+    ref = reference(L, spin, color, ncols, vals, kron, jj, x, alpha, beta, y0, power)
+    dim = [L, L, L, L, spin, color]
+    full = [([0] * 6, dim)]
+    blk, kr = [1, 1, 1, 1, 1, color], [1, 1, 1, 1, spin, 1]
+    op = sb.create_kron_bsr(full, dim, full, dim, blk, blk, kr, kr, False,
+                            [torch.from_numpy(ii).to(gpu)], [torch.from_numpy(jj).to(gpu)],
+                            [torch.from_numpy(vals).to(gpu)], [torch.from_numpy(kron).to(gpu)])
+    dimx = [1, L, L, L, L, color, ncols, spin]
+    dimy = [power] + dimx[1:]
+    keys = ("bsr.kron_mfma_min_cols", "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds",
+            "bsr.kron_spin", "bsr.kron_mfma")
+    old = [sb.tune_get(k) for k in keys]
+    variants = ((1, 1, 0), (1, 3, 1), (1, 0, 0), (0, 2, 1))
+    outs = []
+    try:
+        sb.tune_set("bsr.kron_mfma_min_cols", 1)
+        sb.tune_set("bsr.kron_spin", 0)
+        sb.tune_set("bsr.kron_mfma", 1)
+        for pack, xl, yl in variants:
+            sb.tune_set("bsr.kron_pack", pack)
+            sb.tune_set("bsr.kron_xlds", xl)
+            sb.tune_set("bsr.kron_ylds", yl)
+            ty = torch.from_numpy(y0.copy()).to(gpu)
+            sb.bsr_krylov(alpha, op, "xyztsc", "XYZTSC", [([0] * 8, dimx)], "pXYZTCnS", [0] * 8,
+                          dimx, dimx, [torch.from_numpy(x).to(gpu)], beta, [([0] * 8, dimy)],
+                          "pxyztcns", [0] * 8, dimy, dimy, "p", [ty])
+            torch.cuda.synchronize()
+            outs.append((sb.tune_get("bsr.last_kernel"), ty.cpu().numpy()))
+    finally:
+        for k, v in zip(keys, old):
+            sb.tune_set(k, v)
+        op.destroy()
+    for (pack, xl, yl), (form, out) in zip(variants, outs):
+        assert form == (6 if pack and ncols in (1, 2, 3, 4, 6) else 5), (pack, xl, yl, form)
+        assert np.array_equal(out, ref), (pack, xl, yl, form)
+
+
 @pytest.mark.parametrize("seed", range(24))
 def test_kron_fuzz(gpu, seed):
     """Random Kronecker operators: lattice 1-4, spin 1 / 2 / 4, color 1-3, rhs columns 1-300

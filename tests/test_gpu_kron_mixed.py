@@ -147,6 +147,36 @@ def test_kron_mixed_forward_forms(gpu, ncols, L, form, bif, sparse):
         assert np.array_equal(out, ref), kernel
 
 
+@pytest.mark.parametrize("ncols", [1, 2, 3, 4, 5, 6, 7])
+def test_kron_mixed_low_columns(gpu, ncols):
+    """the matrix-core forms below 8 columns ("bsr.kron_mfma_min_cols" 1), 3^4 sites: the packed
+    kernel with 2-4 waves and 32, 32, 16, 16 and 8 rows per workgroup at 1, 2, 3, 4 and 6 columns,
+    the one-row-per-wave kernel at 5 and 7 and with packing off; a short last workgroup in each"""
+    import superbblas_amd as sb
+    L, spin, color, power = 3, 4, 3, 2
+    ii, jj, vals, kron, x, y0, ref = forward_case(L, spin, color, ncols, False, False, power)
+    op, _, _ = make_op(sb, gpu, L, color, color, spin, spin, False, ii, jj, vals, kron, C64)
+    keys = ("bsr.kron_mfma_min_cols", "bsr.kron_pack", "bsr.kron_xlds", "bsr.kron_ylds", "bsr.kron_spin",
+            "bsr.kron_mfma")
+    old = [sb.tune_get(k) for k in keys]
+    variants = ((1, 1, 0), (1, 3, 1), (1, 0, 0), (0, 2, 1))
+    outs = []
+    try:
+        for pack, xl, yl in variants:
+            for k, v in zip(keys, (1, pack, xl, yl, 0, 1)):
+                sb.tune_set(k, v)
+            outs.append(apply(sb, gpu, op, L, color, color, spin, spin, ncols, x, C128, ALPHA, BETA, y0,
+                              power))
+    finally:
+        for k, v in zip(keys, old):
+            sb.tune_set(k, v)
+        op.destroy()
+    for (pack, xl, yl), (kernel, mixed, out) in zip(variants, outs):
+        assert kernel == (6 if pack and ncols in (1, 2, 3, 4, 6) else 5), (pack, xl, yl, kernel)
+        assert mixed == 1
+        assert np.array_equal(out, ref), (pack, xl, yl, kernel)
+
+
 def test_kron_mixed_spin_first_not_taken(gpu):
     """bsr.kron_spin 1 / 2 (the spin-first kernels read tables of doubles): a mixed launch keeps
     the matrix-core form and the result"""

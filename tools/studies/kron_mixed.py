@@ -16,7 +16,8 @@ process; every figure is the library's HIP-event time of the "bsr" kernels over 
      without the mixed product -- code this change leaves as it was, the yardstick
   a  A^H x, complex<float> operator, the default dispatch (bsr_kron_adj_kernel)
   h  A^H x, the widened operator, the default dispatch
-FORMS selects among them (default mvxdah).  One JSON line per point: the median of the rounds and
+FORMS selects among them (default mvxdah); XLDS, if set, is "bsr.kron_xlds" for the whole run (the
+matrix-core kernels' instantiations with x staged that many neighbours ahead).  One JSON line per point: the median of the rounds and
 their spread (max - min) per form, the algorithmic bytes -- ev (81 V + 144) + 16 (2 12 V n) +
 4 (9 V) with ev the bytes of a value (8 or 16) --, their fraction of 8 TB/s, and the ratios
 v / m (above 1: the matrix-core form is the faster mixed form), d / x (above 1: the mixed product
@@ -80,6 +81,8 @@ def main():
     tag = os.environ.get("TAG", "")
     g = torch.Generator(device=dev).manual_seed(7)
     sb.tune_set("bsr.kron_mixed", 1)
+    if os.environ.get("XLDS"):
+        sb.tune_set("bsr.kron_xlds", int(os.environ["XLDS"]))
     for lat in lats:
         V = int(np.prod(lat))
         jj = torch.from_numpy(stencil(lat).reshape(-1)).to(dev)

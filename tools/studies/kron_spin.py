@@ -16,6 +16,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+if os.environ.get("SB_ROOT"):  # another tree's build of the library (a comparison of two builds)
+    sys.path.insert(0, os.environ["SB_ROOT"])
 import superbblas_amd as sb  # noqa: E402
 from bsr_bound import columns  # noqa: E402
 from kron_bound import spin_matrices  # noqa: E402
