@@ -642,7 +642,11 @@ void contraction(T alpha, const PartitionItem<Nd0> *p0, const Coor<Nd0> &from0,
 /// float / std::complex<float>; the values are widened to float exactly where they are read, and
 /// products, sums, alpha, beta and y are float.  binary16 holds magnitudes up to 65504 (smallest
 /// subnormal 2^-24): scale the operator into range and pass the scale in alpha.  Half operators
-/// with double vectors and create_kron_bsr with half values throw (whatever bsr.kron_mixed).
+/// with double vectors throw.  create_kron_bsr<Nd, Ni, float16> and <Nd, Ni, complex_float16>
+/// (colour values and spin matrices both in that type) throw "unsupported type" whatever
+/// bsr.kron_mixed -- unless sbx_tune_set("bsr.kron_half", 1) (default 0): then the operator is
+/// created and, with the key still at 1 at the bsr_krylov call, contracted with T = float /
+/// std::complex<float>, A x and A^H x, both arrays read in place and widened where they are read.
 ///
 /// The image side (x with the image labels, y = alpha A^H x) of a create_bsr operator: by default
 /// the first such product makes a conjugated, regrouped copy of the value blocks that all later

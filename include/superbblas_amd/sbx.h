@@ -147,8 +147,14 @@ int sbx_timings_report(char *buf, int len);
    "bsr.kron_mixed" (operators of sbx_create_kron_bsr in float / complex<float>, values and spin matrices,
    applied to double / complex<double> vectors; read at each sbx_bsr_krylov call: 0, the default, refused --
    any type difference on a Kronecker operator fails; 1 admitted, A x and A^H x, both arrays read in place and
-   widened at the load, products and sums in double; half-precision Kronecker values stay refused at creation
+   widened at the load, products and sums in double; half-precision Kronecker values are not its business ("bsr.kron_half")
    and the spin-first kernels of "bsr.kron_spin" are not taken),
+   "bsr.kron_half" (operators of sbx_create_kron_bsr in SBX_HALF / SBX_CHALF, values and spin matrices: 0, the
+   default, refused at creation with "unsupported type", whatever "bsr.kron_mixed"; 1 created, and -- the key
+   read again at each sbx_bsr_krylov call, a handle made under 1 is refused while it is 0 -- applied to float /
+   complex<float> vectors, A x and A^H x, both arrays read in place and widened exactly at the load, products
+   and sums in float, on the VALU Kronecker kernels; under double or half vectors, or real with complex, they
+   stay refused),
    "dense.wave", "dist.reduce" (must be set alike on every rank: the ranks' reductions must
    match; SB_DEBUG >= 1 checks it), "dist.force_peer" (1: the several-GPUs-per-rank path -- pack, hipMemcpyPeerAsync, unpack -- for every piece between components of a rank even on one device), "alloc.max_cached", "debug.level" (overrides SB_DEBUG),
    "debug.corrupt_copy" (tests of the SB_DEBUG checks: drop that local piece of every copy); read-backs "bsr.last_kernel" (the form of the
@@ -156,7 +162,8 @@ int sbx_timings_report(char *buf, int len);
    its mixed form, 0 with it = the generic kernel bsr_kernel's mixed form, 7 / 8 / 10 / 11 with it = the 12x12
    matrix-core kernels reading the narrower values, 5 / 6 / 15 with it = the Kronecker kernels reading
    single-precision values under "bsr.kron_mixed", 19 = the generic Kronecker adjoint kernel doing so (16 without
-   "bsr.last_mixed"); 17 = bsr_blk_mfma_kernel's and 18 =
+   "bsr.last_mixed"), 15 / 19 / 0 with it under float vectors = the Kronecker kernels reading half-precision
+   values under "bsr.kron_half"; 17 = bsr_blk_mfma_kernel's and 18 =
    bsr_kernel's adjoint form, the in-place adjoint of "bsr.adj_inplace" 1), "bsr.adj_copy_bytes" (the bytes currently held
    by the value copies of transposed operators, process-wide: it grows when a copy is made and shrinks when
    its operator is destroyed; it cannot be set), "bsr.last_mixed" (1 when the last BSR
@@ -310,7 +317,9 @@ int sbx_create_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const
    y = alpha A^H x (beyond the reference, whose local Kronecker operators throw "unsupported
    conjugation", bsr.h:399, 1032); A^H reads v and kronv in place, conj-transposed, so it follows
    changes made to them just as A does.  t is one of the four floating-point tensor types:
-   SBX_HALF / SBX_CHALF fail with "unsupported type". */
+   SBX_HALF / SBX_CHALF fail with "unsupported type" -- unless the tune key "bsr.kron_half" is 1
+   (default 0): then v and kronv are both IEEE binary16 values in that type, and sbx_bsr_krylov
+   applies the operator to SBX_FLOAT / SBX_CFLOAT vectors while the key is 1 (see there). */
 int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, const int *pdm,
                         const int *dimd, int ncomponents, const int *blockim, const int *blockdm,
                         const int *kronim, const int *krondm, int blockImFast,
@@ -333,6 +342,9 @@ int sbx_create_kron_bsr(int nd, int ni, int t, const int *pim, const int *dimi, 
    one.  The binary16 values are converted to float exactly (subnormals included) where they are
    loaded; products, sums, alpha, beta and y are float.  binary16 holds magnitudes up to 65504
    (smallest subnormal 2^-24): scale the operator into range and pass the scale in alpha.
+   Operators of sbx_create_kron_bsr take part under their tune keys only, each read at every
+   call: SBX_FLOAT / SBX_CFLOAT ones under double vectors with "bsr.kron_mixed" 1, SBX_HALF /
+   SBX_CHALF ones under float vectors with "bsr.kron_half" 1 (v and kronv both read in place).
    Every other difference of types -- a half operator with double or half vectors among them --
    fails with the same errors as before and leaves y untouched. */
 int sbx_bsr_krylov(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, const double *alpha,

@@ -729,7 +729,10 @@ def create_kron_bsr(pim, dimi, pdm, dimd, blockim, blockdm, kronim, krondm, bloc
                     v: Sequence[torch.Tensor], kronv: Sequence[torch.Tensor],
                     co: int = SlowToFast, comm: Optional[Comm] = None) -> BSR:
     """create_kron_bsr<Nd,Ni,T> (bsr.h:2476-2490): create_bsr plus, per component, kronv[c] =
-    one volume(kronim) x volume(krondm) matrix per nonzero position of a block row."""
+    one volume(kronim) x volume(krondm) matrix per nonzero position of a block row.  v and kronv
+    share one type: float32 / float64 / complex64 / complex128, or -- under
+    tune_set("bsr.kron_half", 1) only (default 0: "unsupported type") -- torch.float16 /
+    torch.complex32, IEEE binary16 values that bsr_krylov applies to float32 / complex64 vectors."""
     nd, ni = len(dimd), len(dimi)
     nc = len(v)
     h = ctypes.c_void_p()
@@ -757,7 +760,11 @@ def bsr_krylov(alpha, bsr: BSR, oim: str, odm: str, px, ox: str, fromx, sizex, d
     place, widened exactly where they are loaded, and the product is computed and written in
     double (no converted copy is kept).  An operator of create_kron_bsr in float32 / complex64
     (values and spin matrices) is admitted in the same way, A x and A^H x, under
-    tune_set("bsr.kron_mixed", 1) only (default 0).  Any other difference of types raises."""
+    tune_set("bsr.kron_mixed", 1) only (default 0).  The same one step down: an operator of
+    create_bsr in float16 / complex32 is applied to float32 / complex64 vx and vy (widened exactly
+    at the load, products and sums in FP32), and one of create_kron_bsr in float16 / complex32
+    under tune_set("bsr.kron_half", 1) only (default 0; the key is read at each call).  Any other
+    difference of types raises."""
     nx, ny = len(ox), len(oy)
     nc = len(vx)
     t = _dtype_of(list(vx) + list(vy))

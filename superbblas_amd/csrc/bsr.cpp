@@ -805,16 +805,12 @@ void krylov(const BsrOp &op, const Scalar &alpha, const std::string &oi, const s
             (op.kroni[i] > 1 && op.kroni[i] != op.dimi[i]))
             throw Error("Still not supported partially blocking a dimension");
     // x and y have the operator's type, or -- an extension -- a single-precision operator is
-    // applied to vectors of its double counterpart (a Kronecker operator under bsr.kron_mixed 1
-    // only, read here: its colour blocks and spin matrices), or a half-precision one (never a
-    // Kronecker operator) to vectors of its single counterpart: the values are read in place and
-    // widened at the load, everything else (temporaries, halo exchange, copies) is in x's type
-    const bool to_double = (op.dtype == SBX_FLOAT && x.dtype == SBX_DOUBLE) ||
-                           (op.dtype == SBX_CFLOAT && x.dtype == SBX_CDOUBLE);
-    const bool mixed = op.is_kron ? to_double && g_bsr_tune.kron_mixed != 0
-                                  : to_double || (op.dtype == SBX_HALF && x.dtype == SBX_FLOAT) ||
-                                        (op.dtype == SBX_CHALF && x.dtype == SBX_CFLOAT);
-    if (x.dtype != y.dtype || (x.dtype != op.dtype && !mixed))
+    // applied to vectors of its double counterpart, or a half-precision one to vectors of its
+    // single counterpart (bsr_mixed_pair: a Kronecker operator, its colour blocks and spin
+    // matrices, under bsr.kron_mixed / bsr.kron_half 1 only, read here): the values are read in
+    // place and widened at the load, everything else (temporaries, halo exchange, copies) is in
+    // x's type
+    if (x.dtype != y.dtype || (x.dtype != op.dtype && !bsr_mixed_pair(op.dtype, op.is_kron, x.dtype)))
         throw Error("bsr_krylov: type mismatch");
     const int dtype = x.dtype;
     const std::size_t es = dtype_size(dtype);

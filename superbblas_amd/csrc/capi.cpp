@@ -462,6 +462,7 @@ int sbx_tune_set(const char *key, long long value) {
         else if (k == "bsr.mixed12_pack") g_bsr_tune.mixed12_pack = (int)value;
         else if (k == "bsr.adj_inplace") g_bsr_tune.adj_inplace = (int)value;
         else if (k == "bsr.kron_mixed") g_bsr_tune.kron_mixed = (int)value;
+        else if (k == "bsr.kron_half") g_bsr_tune.kron_half = (int)value;
         else if (k == "bsr.adj_copy_bytes") throw Error("tune_set: bsr.adj_copy_bytes is read-only");
         else if (k == "bsr.tile") g_bsr_tune.tile = (int)value;
         else if (k == "bsr.tile_min_cols") g_bsr_tune.tile_min_cols = value;
@@ -548,6 +549,7 @@ int sbx_tune_get(const char *key, long long *value) {
         else if (k == "bsr.last_mixed") *value = g_bsr_tune.last_mixed;
         else if (k == "bsr.adj_inplace") *value = g_bsr_tune.adj_inplace;
         else if (k == "bsr.kron_mixed") *value = g_bsr_tune.kron_mixed;
+        else if (k == "bsr.kron_half") *value = g_bsr_tune.kron_half;
         else if (k == "bsr.adj_copy_bytes") *value = g_bsr_tune.adj_copy_bytes;
         else if (k == "gemm.m3") *value = g_gemm_tune.m3;
         else if (k == "gemm.splits") *value = g_gemm_tune.splits;
@@ -1029,8 +1031,10 @@ int create_bsr_any(int nd, int ni, int t, const int *pim, const int *dimi, const
     return guard([&] {
         check_session(session);
         if (!bsrh) throw Error("create_bsr: null handle output");
-        // the half-precision value types: operators of sbx_create_bsr only
-        if (kronv && dtype_is_half(t)) throw Error("create_kron_bsr: unsupported type");
+        // the half-precision value types: operators of sbx_create_bsr, and of sbx_create_kron_bsr
+        // under bsr.kron_half 1
+        if (kronv && dtype_is_half(t) && g_bsr_tune.kron_half == 0)
+            throw Error("create_kron_bsr: unsupported type");
         const Comm c = get_comm(comm);
         const bool rev = co == SBX_FAST_TO_SLOW;
         std::vector<const int *> vii, vjj;
@@ -1105,15 +1109,9 @@ int sbx_bsr_krylov_req(sbx_bsr bsrh, int nd, int ni, int nx, int ny, int t, cons
     return guard([&] {
         check_session(session);
         if (!bsrh || !bsrh->op) throw Error("bsr_krylov: invalid handle");
-        // T is the operator's type, or the double counterpart of a single-precision operator
-        // (Kronecker operators: under bsr.kron_mixed 1 only) or the single counterpart of a
-        // half-precision one (never a Kronecker operator): the mixed products of bsr.cpp
-        const bool to_double = (bsrh->dtype == SBX_FLOAT && t == SBX_DOUBLE) ||
-                               (bsrh->dtype == SBX_CFLOAT && t == SBX_CDOUBLE);
-        const bool mixed = bsrh->is_kron ? to_double && g_bsr_tune.kron_mixed != 0
-                                         : to_double || (bsrh->dtype == SBX_HALF && t == SBX_FLOAT) ||
-                                               (bsrh->dtype == SBX_CHALF && t == SBX_CFLOAT);
-        if (bsrh->nd != nd || bsrh->ni != ni || (bsrh->dtype != t && !mixed))
+        // T is the operator's type, or one of the mixed products' pairs (bsr_mixed_pair)
+        if (bsrh->nd != nd || bsrh->ni != ni ||
+            (bsrh->dtype != t && !bsr_mixed_pair(bsrh->dtype, bsrh->is_kron, t)))
             throw Error("Given BSR handle doesn't match the template parameters Nd, Ni, or T");
         if (co != bsrh->co)
             throw Error("Unsupported to use a different coordinate ordering that one used to "

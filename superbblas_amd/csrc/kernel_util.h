@@ -52,6 +52,24 @@ template <> struct Uniform<float2> {
     }
 };
 
+/// A binary16 element: scalar loads move whole dwords, and for a 2-byte element behind a pointer
+/// that is only 2-byte aligned the compiler gives the scalar load up (global_load_ushort into a
+/// VGPR per element).  Instead: the aligned dword that holds the element, then its low or high
+/// half by the address's bit 1 -- right for an odd index and for a base that is 2 mod 4.  The
+/// other half of that dword may lie just outside the array (its first element at 2 mod 4, or its
+/// last at 0 mod 4); an aligned dword never crosses a page or an allocation granule, and that
+/// half is dropped.  (A pair of binary16, 4-byte aligned, is one s_load_dword by the generic form.)
+template <> struct Uniform<_Float16> {
+    static __device__ __forceinline__ _Float16 load(const _Float16 *p, long i) {
+        const size_t a = (size_t)(p + i);
+        const unsigned w = *(ConstPtr<unsigned>)(a & ~(size_t)3);
+        const unsigned short h = (unsigned short)((a & 2) ? w >> 16 : w);
+        _Float16 r;
+        __builtin_memcpy(&r, &h, 2);
+        return r;
+    }
+};
+
 // LDS-DMA: a lane's 16 (dma4: 4) bytes at buffer offset `off` of `rs` go to LDS address dst +
 // 16 (4) * lane; dst is wave-uniform (m0), an offset past the buffer writes zeros.
 // Inline asm: hipcc does not order its ds_reads against an LDS-DMA it cannot see; the kernel

@@ -59,6 +59,8 @@ __device__ __forceinline__ void store_outputs(E *ys, long n, double alpha_re, do
 // type EV beside the vector type E -- EV = E, or float / float2 under double / double2.  The
 // colour blocks v and the spin matrices kron are read in place as EV and widened (to_vec, exact)
 // where they are read; x, y, products, sums and alpha are E.  No converted copy exists.
+// Half precision (bsr.kron_half): the same one step down, EV = f16 / f16x2 under float / float2,
+// on the VALU kernels (the matrix-core forms are complex<double> vectors only).
 template <typename EV, typename E, int BI, int BD, int KI, int KD>
 __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
     const EV *__restrict__ v = (const EV *)p.v;
@@ -114,6 +116,12 @@ __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
     }
 }
 
+/// Bytes of bsr_kron_lds_kernel's LDS image of `nvalues` values of EV, a multiple of 4: the block
+/// columns (ints) follow it
+template <typename EV> constexpr long kron_lds_values_bytes(long nvalues) {
+    return (nvalues * (long)sizeof(EV) + 3) / 4 * 4;
+}
+
 /// Many rhs columns: a workgroup owns `S` consecutive block rows x up to 256 columns; the color
 /// blocks of its rows (S * NNZ * BI * BD values, contiguous in memory) and their domain sites are
 /// staged in LDS with coalesced loads (instead of every lane of a row fetching the same 9 blocks
@@ -122,12 +130,19 @@ __global__ void __launch_bounds__(256) bsr_kron_kernel(const KronArgs p) {
 /// while the current one is being applied (the loop over the NNZ nonzeros is unrolled).
 /// Mixed: the LDS image Us holds the values as stored (EV: half the LDS), widened at the LDS read;
 /// the spin matrices are scalar loads of EV, widened on the scalar side's way into the FMAs.
+/// 2-byte values (f16 under float): S * BLK of them are an odd number of halves for odd S (5, 10
+/// and 17 columns: S = 51, 25, 15), so the values' image is padded to whole dwords and Js stays
+/// 4-byte aligned (kron_lds_values_bytes: the kernel's and the launcher's one statement of it).
+/// The staging is one element per load: exact at both ends of the run for a value array that is
+/// only element-aligned and that ends with the last row's last value.
 template <typename EV, typename E, int BI, int BD, int KI, int KD, int NNZ>
 __global__ void __launch_bounds__(256) bsr_kron_lds_kernel(const KronArgs p, int S, int cpg) {
     extern __shared__ char smem[];
     constexpr int BLK = BI * BD * NNZ;
     EV *Us = (EV *)smem;
-    int *Js = (int *)(Us + (long)S * BLK);
+    int *Js;
+    if constexpr (sizeof(EV) % 4 == 0) Js = (int *)(Us + (long)S * BLK);
+    else Js = (int *)(smem + kron_lds_values_bytes<EV>((long)S * BLK));
     const EV *__restrict__ v = (const EV *)p.v;
     const EV *kron = (const EV *)p.kron;
     const E *__restrict__ x = (const E *)p.x;
@@ -885,7 +900,7 @@ constexpr int KRON_ADJ_CHUNK = 160, KRON_ADJ_SITES = 16, KRON_ADJ_STAGE_COLS = 3
 /// lanes consecutive columns, contiguous KI-element pieces -- one entry ahead, does the color
 /// product t(d, a) = sum_i conj(U(i, d)) x(i, a), then the spin product
 /// acc(d, b) += sum_a conj(K(a, b)) t(d, a), skipping the zeros of K.
-/// Mixed (EV narrower than E, bsr.kron_mixed): the conj-transposed images Us and Ks are widened
+/// Mixed (EV narrower than E, bsr.kron_mixed and bsr.kron_half): the conj-transposed images Us and Ks are widened
 /// where they are staged, so the LDS layout and size are those of the same-type kernel of E and
 /// the main loop is unchanged; a lane reading its blocks itself widens at the load.
 template <typename EV, typename E, int BI, int BD, int KI, int KD, bool STAGE>
@@ -1051,8 +1066,8 @@ int kron_xl(const KronArgs &a) {
     return fits ? std::max(0, std::min(3, g_bsr_tune.kron_xlds)) : 0;
 }
 
-/// f(EV{}, E{}) with EV the values' type and E the vectors': the same type, or single-precision
-/// values under double vectors
+/// f(EV{}, E{}) with EV the values' type and E the vectors': the same type, single-precision
+/// values under double vectors, or half-precision values under single vectors
 template <typename F> void with_kron_types(const BsrDesc &d, F f) {
     if (d.tv == d.t) switch (d.t) {
         case SBX_CDOUBLE: return f(double2{}, double2{});
@@ -1063,10 +1078,13 @@ template <typename F> void with_kron_types(const BsrDesc &d, F f) {
         }
     if (d.tv == SBX_CFLOAT && d.t == SBX_CDOUBLE) return f(float2{}, double2{});
     if (d.tv == SBX_FLOAT && d.t == SBX_DOUBLE) return f(float{}, double{});
+    if (d.tv == SBX_CHALF && d.t == SBX_CFLOAT) return f(f16x2{}, float2{});
+    if (d.tv == SBX_HALF && d.t == SBX_FLOAT) return f(f16{}, float{});
     throw Error("kron bsr: unsupported type");
 }
 
-/// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
+/// EV: the values' type, E: the vectors' (EV = E, float / float2 under double / double2, or
+/// f16 / f16x2 under float / float2)
 template <typename EV, typename E> void launch_kron_adj_typed(const KronAdjArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
     if (g_bsr_tune.kron_adj && is_3x3_4x4(a)) {
@@ -1124,12 +1142,16 @@ void launch_bsr_kron_adj(const BsrDesc &d, int device) {
     with_kron_types(d, [&](auto ev, auto e) { launch_kron_adj_typed<decltype(ev), decltype(e)>(a, s); });
 }
 
-/// EV: the values' type, E: the vectors' (EV = E, or float / float2 under double / double2)
+/// EV: the values' type, E: the vectors' (EV = E, float / float2 under double / double2, or
+/// f16 / f16x2 under float / float2)
 template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hipStream_t s) {
     KernelTimer timer("bsr", s);
     constexpr bool same = std::is_same<EV, E>::value;
-    // (bsr_kron_lds_kernel's LDS image holds the values as stored)
-    const long row_bytes = (long)a.nnz * (a.bi * a.bd * sizeof(EV) + sizeof(int));
+    // (bsr_kron_lds_kernel's LDS image holds the values as stored, padded to whole dwords, then
+    // the block columns)
+    auto lds_rows = [&](long S) {
+        return kron_lds_values_bytes<EV>(S * a.nnz * a.bi * a.bd) + S * a.nnz * (long)sizeof(int);
+    };
     // the spin-first kernels read their tables of doubles: same-type products only
     if constexpr (std::is_same<E, double2>::value && same) {
         if (g_bsr_tune.kron_spin == 2 && a.xtab && is_3x3_4x4(a) && a.nnz >= 1 &&
@@ -1232,12 +1254,12 @@ template <typename EV, typename E> void launch_kron_typed(const KronArgs &a, hip
         }
     }
     if (is_3x3_4x4(a) && a.nnz == 9 && a.ncols >= 4 &&
-        row_bytes * (256 / std::min<long>(a.ncols, 256)) <= KRON_LDS_BYTES) {
+        lds_rows(256 / std::min<long>(a.ncols, 256)) <= KRON_LDS_BYTES) {
         const int cpg = (int)std::min<long>(a.ncols, 256);
         const int S = 256 / cpg;
         const dim3 grid((unsigned)((a.block_rows + S - 1) / S), (unsigned)((a.ncols + cpg - 1) / cpg));
         hipLaunchKernelGGL((bsr_kron_lds_kernel<EV, E, 3, 3, 4, 4, 9>), grid, dim3(256),
-                           (size_t)(row_bytes * S), s, a, S, cpg);
+                           (size_t)lds_rows(S), s, a, S, cpg);
     } else if (is_3x3_4x4(a)) {
         const long total = a.block_rows * a.ncols;
         const long blocks = std::min((total + 255) / 256, 65536L);

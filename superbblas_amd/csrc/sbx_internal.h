@@ -379,6 +379,13 @@ struct BsrTune {
                         ///< widened at the load, everything else is FP64 (the kernels of
                         ///< kernels_bsr_kron.hip with a value type beside the vector type; the
                         ///< spin-first kernels, kron_spin 1 / 2, are not taken)
+    int kron_half = 0; ///< operators of create_kron_bsr kept in float16 / complex32 (IEEE binary16; colour
+                       ///< blocks and spin matrices): 0 = refused at the creation ("unsupported type") and,
+                       ///< read again at each bsr_krylov call, at the product of a handle made under 1;
+                       ///< 1 = admitted, and applied to float / complex<float> vectors, A x and A^H x: the
+                       ///< values are read in place and widened at the load (exact, subnormals included),
+                       ///< everything else is FP32 (the VALU kernels of kernels_bsr_kron.hip; single
+                       ///< vectors have no matrix-core form).  Independent of kron_mixed
     /// read-back ("bsr.adj_copy_bytes"): bytes held by the value copies of transposed operators,
     /// process-wide (grows when a copy is made, shrinks when its operator is destroyed)
     std::atomic<long long> adj_copy_bytes{0};
@@ -399,13 +406,29 @@ struct BsrTune {
     /// output element, single-precision values under double-precision vectors (kron_mixed),
     /// 0 another kernel.  7, 8, 10 and 11 with last_mixed 1: the same 12x12 kernels reading values of
     /// the narrower type (mixed12_min_cols, mixed12_pack); 5, 6 and 15 with last_mixed 1: the same
-    /// Kronecker kernels reading single-precision values (kron_mixed)
+    /// Kronecker kernels reading single-precision values (kron_mixed).  Half-precision Kronecker
+    /// values under single vectors (kron_half) report 15 and 19 in the same way, and 0 forward
     std::atomic<int> last{0};
     /// read-back ("bsr.last_mixed"): 1 when the last BSR launch read values of a narrower type
     /// than its vectors, else 0
     std::atomic<int> last_mixed{0};
 };
 extern BsrTune g_bsr_tune;
+
+/// The mixed products of bsr_krylov: whether an operator whose values have the type `op` (made by
+/// create_kron_bsr: `is_kron`) is applied to vectors of another type `vec`, its values read in
+/// place and widened exactly at the load.  The one statement of the rule (the C ABI's handle check
+/// and bsr_krylov both ask here; the tune keys are read at each call):
+///   float -> double, complex<float> -> complex<double>      Kronecker: under kron_mixed 1 only
+///   float16 -> float, complex32 -> complex<float>           Kronecker: under kron_half 1 only
+/// Every other pair of different types is none: real with complex, half with double, a wider
+/// operator under narrower vectors
+inline bool bsr_mixed_pair(int op, bool is_kron, int vec) {
+    const bool to_double = (op == SBX_FLOAT && vec == SBX_DOUBLE) || (op == SBX_CFLOAT && vec == SBX_CDOUBLE);
+    const bool to_single = (op == SBX_HALF && vec == SBX_FLOAT) || (op == SBX_CHALF && vec == SBX_CFLOAT);
+    if (!is_kron) return to_double || to_single;
+    return (to_double && g_bsr_tune.kron_mixed != 0) || (to_single && g_bsr_tune.kron_half != 0);
+}
 /// dense solvers: matrices up to 16 x 16 packed 64 / n per wave -- 1: Cholesky and LU
 /// (inversion, gesm), 2: the triangular solves too (the default); 0 = the workgroup-per-matrix
 /// kernels
